@@ -7,10 +7,22 @@ BASELINE.md's synthetic bytes: splitmix64 seeded with 0xF11EDA6 ^ b (b = the blo
 the whole job), generated on the device.  One step = encode every block
 (dag/node/dagnode/erasure.go:60) then ReconstructData of a lost data shard 0 for every block
 (erasure.go:82, the DagNode.Get path), both through the C-ABI (include/rsmi.h) on one HIP
-stream.  After the timed steps the run checks itself: every lost row is erased and rebuilt
-and compared with its original bytes on the device, every data row is compared with a fresh
-copy of the generator's output, and the parity of sampled blocks is compared with the CPU
-oracle (test infrastructure, never the thing measured).  A mismatch exits non-zero.
+stream.  A plain run sets up, settles, warms up, times the `--steps` steps and prints its line.
+
+`--dump-outputs DIR` writes what the last timed step computed, before anything else touches
+the buffers: `parity.npy` (the encode's parity rows) and `rebuilt.npy` (the reconstruct's
+rebuilt rows) as float32 arrays (blocks, rows, S) over a fixed, seeded sample of this rank's
+blocks (at most 64 MB in all), `crc.npy` (every block's raw fused CRC words, float64) with
+`--fused-crc`.  The inputs are a function of the arguments alone, so two builds can be compared
+output for output.  Rank 0 writes them.
+
+`--full` adds the legs that take runs of their own.  After the timed steps it times
+`--sustained-steps` more back to back (`sustained`), then checks itself: every lost row is
+erased and rebuilt and compared with its original bytes on the device, every data row is
+compared with a fresh copy of the generator's output, and the parity of sampled blocks is
+compared with the CPU oracle (test infrastructure, never the thing measured); a mismatch
+exits non-zero.  Last comes `cpu_baseline` (below).  Without `--full` the line carries
+`verify.skipped`, no `sustained` and a null `cpu_baseline`.
 `--config` selects the other BASELINE configs, `--layout split` the contiguous Split layout
 (rows back to back at pitch S, as blocks arrive from the Put path) and `--fused-crc` the
 encode with the datanode CRC-16 of every shard fused in (DagNode.Put's form) as side lines.
@@ -23,8 +35,8 @@ barrier, the max-over-ranks reduction and the per-rank roofline figures.
 
 Prints ONE JSON line (rank 0).  roofline.achieved is the encode kernel's algorithmic bytes
 ((k+m)*S per block) per launch divided by its average launch time, measured with HIP events
-on the launch stream inside the timed region; cpu_baseline times the oracle's multi-threaded
-SIMD restatement (oracle/rs_cpu_fast.c) on the same blocks on this host's cores.
+on the launch stream inside the timed region; cpu_baseline (`--full`) times the oracle's
+multi-threaded SIMD restatement (oracle/rs_cpu_fast.c) on the same blocks on this host's cores.
 """
 import argparse
 import json
@@ -75,13 +87,20 @@ def parse(argv=None):
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--config", default="rs10_4_256k", choices=sorted(CONFIGS))
     p.add_argument("--blocks", type=int, default=0, help="blocks per GPU (0 = config default)")
-    p.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline time budget (0 = skip)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs beyond the headline figure: the sustained run, the post-run self "
+                        "check and the CPU baseline (--sustained-steps, --no-verify and --cpu-seconds shape them)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the last step computed as DIR/<name>.npy "
+                        "(float32 / float64, a fixed seeded sample of the blocks, at most 64 MB in all)")
+    p.add_argument("--cpu-seconds", type=float, default=10.0,
+                   help="with --full: CPU baseline time budget (0 = skip)")
     p.add_argument("--settle-ms", type=float, default=200.0,
                    help="untimed run of the step before the warmup steps, past the GPU's start-up power "
                         "transient (DESIGN.md section 5); 0 = off")
     p.add_argument("--sustained-steps", type=int, default=200,
-                   help="after the K timed steps, also time this many back to back (reported as "
-                        "`sustained`, never `value`); 0 = off")
+                   help="with --full: after the K timed steps, also time this many back to back (reported "
+                        "as `sustained`, never `value`); 0 = off")
     p.add_argument("--layout", choices=("pitched", "split"), default="pitched",
                    help="pitched: rows at rsmi_recommended_pitch (the batch API's layout); split: the "
                         "contiguous Split layout, rows back to back at pitch S")
@@ -103,13 +122,15 @@ def parse(argv=None):
                    help="time the kernels of every N-th timed step with HIP events (3 per sampled step); "
                         "each event between kernels costs the step ~3 us (tools/eventgap.py), so the "
                         "other steps run uninstrumented.  1 = every step")
-    p.add_argument("--no-verify", action="store_true", help="skip the post-run self check")
+    p.add_argument("--no-verify", action="store_true", help="with --full: skip the post-run self check")
     p.add_argument("--mock", action="store_true",
                    help="test only: a CPU stand-in for the device step, to exercise the launcher, the "
                         "ranks and the JSON line on a host without a GPU; never a measurement")
     a = p.parse_args(argv)
     if a.steps < 1 or a.warmup < 0 or a.event_every < 1:
         p.error("--steps and --event-every must be at least 1, --warmup at least 0")
+    if not a.full:  # a plain run does only what its headline figure needs
+        a.cpu_seconds, a.sustained_steps, a.no_verify = 0.0, 0, True
     return a
 
 
@@ -467,6 +488,31 @@ def copy_inclusive(codec, k, m, S, nb, lost, data_only, world, group=None):
     return res
 
 
+# ---------------------------------------------------------------- --dump-outputs
+DUMP_BUDGET = 48 << 20  # bytes of float32 rows per run, well inside the 64 MB the option allows
+
+
+def dump_blocks(nb, bytes_per_block):
+    """The blocks --dump-outputs writes: all of them if they fit the budget, else the first, the
+    last and a draw from a generator seeded with SEED -- the same blocks on every run of the
+    same arguments.  bytes_per_block: output bytes (uint8) of one block."""
+    count = max(1, min(nb, DUMP_BUDGET // (4 * bytes_per_block)))
+    if count >= nb:
+        return list(range(nb))
+    if count <= 2:
+        return [0, nb - 1][:count]
+    rng = np.random.default_rng(SEED)
+    return sorted([0, nb - 1] + [int(b) + 1 for b in rng.choice(nb - 2, size=count - 2, replace=False)])
+
+
+def dump_outputs(path, arrays):
+    """DIR/<name>.npy for every array; returns {name: shape} for the JSON line."""
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+    return {name: list(arr.shape) for name, arr in arrays.items()}
+
+
 # ---------------------------------------------------------------- verification
 def verify(codec, lay, buf, first_block, lost, data_only, lost_ref, stream, raw=None, samples=16):
     """Self check after the timed steps.  Returns a dict; raises SystemExit on a mismatch."""
@@ -530,9 +576,11 @@ def run_mock(a, world, rank):
     barrier(world)
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        orc.encode_fast(k, m, data, threads=1)
+        par = orc.encode_fast(k, m, data, threads=1)
     el = max_over_ranks(time.perf_counter() - t0, world)
     per = gather({"rank": rank, "blocks": count}, world)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"parity": par.astype(np.float32)})
     if rank == 0:
         cpu = (cpu_baseline(k, m, S, k * S, data, [], True, min(a.cpu_seconds, 0.2), world)
                if a.cpu_seconds > 0 and world == 1 else None)
@@ -578,7 +626,9 @@ def main():
 
     buf = torch.zeros(nb * bs + 64, dtype=torch.uint8, device=dev)
     lay.fill(buf, first_block, dev)
-    lost_ref = torch.stack([lay.rows(buf, i, i + 1)[:, 0].clone() for i in rec_rows], 1) if rec_rows else None
+    lost_ref = None  # the self check's copy of the rows the reconstruct leg rebuilds
+    if rec_rows and not a.no_verify:
+        lost_ref = torch.stack([lay.rows(buf, i, i + 1)[:, 0].clone() for i in rec_rows], 1)
     base = buf.data_ptr()
     raw = torch.zeros((nb, n), dtype=torch.int32, device=dev) if a.fused_crc else None
 
@@ -652,6 +702,18 @@ def main():
 
     el, enc_t, rec_t = timed(a.steps, a.event_every)
     el_max = max_over_ranks(el, world)
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        # the last timed step's outputs, before the sustained run and the self check write again
+        idx = dump_blocks(nb, (m + len(rec_rows)) * S)
+        sel = torch.as_tensor(idx, dtype=torch.int64, device=dev)
+        arrays = {"parity": lay.rows(buf, k, n)[sel].cpu().numpy().astype(np.float32)}
+        if rec_rows:
+            arrays["rebuilt"] = torch.stack([lay.rows(buf, i, i + 1)[sel, 0] for i in rec_rows], 1).cpu().numpy().astype(
+                np.float32)
+        if raw is not None:
+            arrays["crc"] = raw.cpu().numpy().astype(np.float64)
+        dumped = {"dir": a.dump_outputs, "blocks": len(idx), "arrays": dump_outputs(a.dump_outputs, arrays)}
     sus = None
     if a.sustained_steps > 0:
         sel, _, _ = timed(a.sustained_steps, a.sustained_steps)
@@ -728,6 +790,8 @@ def main():
     }
     if sus:
         out["sustained"] = sus
+    if dumped:
+        out["dumped"] = dumped
     if lost:
         out["reconstruct"] = {
             "kernel": rec_kernel,

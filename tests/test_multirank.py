@@ -73,7 +73,7 @@ def test_bench_spawns_ranks_itself_mock(n):
     import subprocess
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--mock", "--steps", "3"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--mock", "--full", "--steps", "3"],
                          capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -116,7 +116,7 @@ def test_bench_gpus2_share_device_no_launcher():
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1",
-           "--blocks", "256", "--settle-ms", "0", "--sustained-steps", "0", "--share-device"]
+           "--blocks", "256", "--settle-ms", "0", "--full", "--sustained-steps", "0", "--share-device"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -139,7 +139,7 @@ def test_bench_two_ranks_torchrun_on_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", "5", "--warmup", "1", "--blocks", "256", "--settle-ms", "0",
-           "--sustained-steps", "0", "--share-device", "--cpu-seconds", "1"]
+           "--full", "--sustained-steps", "0", "--share-device", "--cpu-seconds", "1"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -238,7 +238,8 @@ def test_launcher_counts_and_spawns_gpu_free(tmp_path):
     assert have >= 1
     assert multi.visible_gpu_count() == have
     out, p = _probe_run(["--gpus", "2", "--share-device", "--steps", "3", "--warmup", "1", "--blocks", "128",
-                         "--settle-ms", "0", "--sustained-steps", "0", "--cpu-seconds", "0"], tmp_path, timeout=300)
+                         "--settle-ms", "0", "--full", "--sustained-steps", "0", "--cpu-seconds", "0"], tmp_path,
+                        timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
     assert p["gpus_counted"] == have and p["hip_libs_mapped"] == [] and p["kfd_fds"] == 0, p
     assert not p["torch_imported"], p

@@ -8,7 +8,7 @@
 #   tests            the whole GPU suite (pytest -m gpu)
 #   pytest:EXPR      the GPU tests matching -k EXPR
 #   smoke            __graft_entry__.smoke()
-#   bench            the headline bench line (bench.py, defaults)
+#   bench            the headline bench line with every leg (bench.py --full)
 #   side             side lines: Split layout, fused CRC-16, configs[4] device group, two ranks
 #   configs          every BASELINE config as a bench line (tools/bench_all_configs.sh)
 #   crcbench         the CRC passes and the fused encode + CRC-16 against the encode
@@ -51,21 +51,21 @@ smoke)
   timeout -k 10 300 python __graft_entry__.py smoke > $O/smoke.log 2>&1 || fail smoke $O/smoke.log
   tail -1 $O/smoke.log ;;
 bench)
-  timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err || fail bench $O/bench.err
+  timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err || fail bench $O/bench.err
   cat $O/bench.json ;;
 side)
   for args in "--layout split" "--fused-crc" "--fused-crc --layout split"; do
     f=$O/side_$(echo $args | tr -d ' -').json
-    timeout -k 10 300 python bench.py $args --cpu-seconds 0 > $f 2> $f.err || fail "bench $args" $f.err
+    timeout -k 10 300 python bench.py $args --full --cpu-seconds 0 > $f 2> $f.err || fail "bench $args" $f.err
     cat $f
   done
-  timeout -k 10 300 python bench.py --config rs16_4_4m --copy-inclusive --group 0,0 --cpu-seconds 0 > $O/side_group.json 2> $O/side_group.err || fail "bench --group" $O/side_group.err
+  timeout -k 10 300 python bench.py --config rs16_4_4m --copy-inclusive --group 0,0 --full --cpu-seconds 0 > $O/side_group.json 2> $O/side_group.err || fail "bench --group" $O/side_group.err
   cat $O/side_group.json
-  timeout -k 10 300 python bench.py --gpus 2 --share-device --cpu-seconds 0 > $O/side_gpus2.json 2> $O/side_gpus2.err || fail "bench --gpus 2" $O/side_gpus2.err
+  timeout -k 10 300 python bench.py --gpus 2 --share-device --full --cpu-seconds 0 > $O/side_gpus2.json 2> $O/side_gpus2.err || fail "bench --gpus 2" $O/side_gpus2.err
   cat $O/side_gpus2.json ;;
 configs)
-  timeout -k 10 900 bash tools/bench_all_configs.sh > $O/configs.txt 2>&1 || fail configs $O/configs.txt
-  cp gpurun_out/cfg_*.json $O/ 2>/dev/null; cat $O/configs.txt ;;
+  timeout -k 10 900 bash tools/bench_all_configs.sh $O > $O/configs.txt 2>&1 || fail configs $O/configs.txt
+  cat $O/configs.txt ;;
 crcbench)
   timeout -k 10 300 python tools/crcbench.py > $O/crcbench.txt 2>&1 || fail crcbench $O/crcbench.txt
   cat $O/crcbench.txt ;;
@@ -74,7 +74,7 @@ fused_ab)
   cat $O/fused_ab.txt ;;
 prof)
   rm -rf $O/prof $O/pmc_fetch $O/pmc_write
-  (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/prof" -o bench -- python3 "$R/bench.py" --cpu-seconds 0 > "$R/$O/prof_bench.json" 2> "$R/$O/prof.err") || fail rocprof $O/prof.err
+  (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/prof" -o bench -- python3 "$R/bench.py" --full --cpu-seconds 0 > "$R/$O/prof_bench.json" 2> "$R/$O/prof.err") || fail rocprof $O/prof.err
   python tools/trace_window.py $O/prof/bench_kernel_trace.csv $O/prof_bench.json $O/trace_window.json | tee $O/prof_window.txt
   (cd /tmp && timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$R/$O/pmc_fetch" -o pmc -- python3 "$R/tools/prof_kernels.py" 5 > "$R/$O/pmc_fetch.log" 2>&1) || fail "pmc fetch" $O/pmc_fetch.log
   (cd /tmp && timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$R/$O/pmc_write" -o pmc -- python3 "$R/tools/prof_kernels.py" 5 > "$R/$O/pmc_write.log" 2>&1) || fail "pmc write" $O/pmc_write.log

@@ -5,12 +5,13 @@
 set -o pipefail
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
+T=$(mktemp -d)  # each run's line and stderr
 for r in 1 2; do
   for lib in "" tools/build/v_*/lib/librsmi.so; do
     [ -z "$lib" ] || [ -e "$lib" ] || continue
-    RSMI_LIB=${lib:+$PWD/$lib} timeout -k 10 200 python bench.py --layout split --cpu-seconds 0 --sustained-steps 0 ${UA_BENCH_ARGS:-} > gpurun_out/ua4.json 2> gpurun_out/ua4.err || { echo "bench failed"; tail gpurun_out/ua4.err; exit 1; }
+    RSMI_LIB=${lib:+$PWD/$lib} timeout -k 10 200 python bench.py --layout split --full --cpu-seconds 0 --sustained-steps 0 ${UA_BENCH_ARGS:-} > $T/ua4.json 2> $T/ua4.err || { echo "bench failed"; tail $T/ua4.err; exit 1; }
     python3 -c "
-import json; j=json.load(open('gpurun_out/ua4.json'))
+import json; j=json.load(open('$T/ua4.json'))
 print(('$lib'.split('/')[2] if '$lib' else 'product').ljust(10), 'encode', j['roofline']['achieved'], '| reconstruct', j['reconstruct']['achieved_GBs'], 'GB/s', j['reconstruct']['kernel'], 'verified', j['verify']['verified'])"
   done
 done | tee gpurun_out/ua4_ab.txt
