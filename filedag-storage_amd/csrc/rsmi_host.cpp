@@ -38,8 +38,8 @@ int repitch(uint8_t* dst, size_t dpitch, const uint8_t* src, size_t spitch, size
 // straight over PCIe: the copy engines were measured running the linear host->device and
 // device->host transfers one after the other, and taking the write-back off them lets it
 // overlap the next chunk's upload (tools/hostsweep.py, RS(10,4) 256 KiB: encode 41.7 -> 47.6
-// GiB/s).  Reconstruct also uploads by kernel loads from such memory (below).  With 2-D
-// DMA rows (S % 8 == 0) the engines already overlap, so that path keeps its copies.
+// GiB/s).  With 2-D DMA rows (S % 8 == 0) the engines already overlap, so that path keeps
+// its copies.
 uint8_t* host_alias(void* p, size_t len) {
     auto alias = [](void* q) -> uint8_t* {
         hipPointerAttribute_t a{};
@@ -273,6 +273,9 @@ int encode_host_impl(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride,
                              ? host_alias(const_cast<uint8_t*>(data), (nblocks - 1) * data_block_stride + k * S)
                              : nullptr;
     const size_t n = k + m;
+    // d_lin holds a chunk's k data rows per block on the way in (the linear upload) and its m
+    // parity rows per block on the way out (the linear write-back), whichever of the two run
+    const size_t lin_rows = d2 ? 0 : std::max(zin ? size_t(0) : k, zc ? size_t(0) : m);
     if (raw_out && (rc = reserve(c->d_crc, c->crc_cap, nblocks * n * 4))) return rc;
     if (raw32_out && (rc = reserve(c->d_crc32, c->crc32_cap, nblocks * n * 4))) return rc;
     for (size_t b0 = 0, i = 0; b0 < nblocks; b0 += chunk, i++) {
@@ -280,7 +283,7 @@ int encode_host_impl(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride,
         const size_t nb = std::min(chunk, nblocks - b0);
         if ((rc = reserve(st.d_in, st.in_cap, nb * in_bs))) return rc;
         if ((rc = reserve(st.d_out, st.out_cap, nb * out_bs))) return rc;
-        if (!d2 && !zin && (rc = reserve(st.d_lin, st.lin_cap, nb * k * S))) return rc;
+        if (lin_rows && (rc = reserve(st.d_lin, st.lin_cap, nb * lin_rows * S))) return rc;
         const uint8_t* src = data + b0 * data_block_stride;
         uint8_t* dst = parity + b0 * parity_block_stride;
         // host -> device
@@ -456,15 +459,8 @@ int reconstruct_host_impl(rsmi_ctx* c, uint8_t* shards, size_t block_stride, siz
     const bool d2 = dma_2d_ok(S);
     const size_t chunk = std::max<size_t>(1, (size_t(64) << 20) / bs);
     const int ns = nblocks > chunk ? 3 : 1;
-    // odd S: rebuilt rows straight into page-locked host memory (see host_alias)
-    uint8_t* zc = c->opt_zero_copy && !d2 ? host_alias(shards, (nblocks - 1) * block_stride + size_t(c->n) * S)
-                                          : nullptr;
-    // the upload by kernel loads too: only the k rows the plan reads cross PCIe, where the
-    // linear copy would ship whole blocks (RS(10,4) 256 KiB batches: 35.5 -> 42.9 GiB/s).
-    // One launch per row, so small calls keep the single linear copy (tools/latency.cpp:
-    // a 4 KiB block took 59 us this way against 26 us with the copy).
-    const uint8_t* zin = nblocks * size_t(c->n) * S >= (size_t(4) << 20) ? zc : nullptr;
-    if (!d2 && !zc) {  // pinned landing area for the rebuilt rows, scattered on the host at the end
+    // (page-locked shards with zero_copy on never get here: they were rebuilt in place above)
+    if (!d2) {  // pinned landing area for the rebuilt rows, scattered on the host at the end
         const size_t need = nblocks * nr * S;
         if (c->h_stage_cap < need) {
             if (c->h_stage) HIP_TRY(hipHostFree(c->h_stage));
@@ -481,12 +477,7 @@ int reconstruct_host_impl(rsmi_ctx* c, uint8_t* shards, size_t block_stride, siz
         const size_t nb = std::min(chunk, nblocks - b0);
         if ((rc = reserve(st.d_in, st.in_cap, nb * bs))) return rc;
         uint8_t* h = shards + b0 * block_stride;
-        if (zin) {  // only the k rows the plan reads cross PCIe
-            for (int r : in_rows)
-                if ((rc = repitch(st.d_in + size_t(r) * Sp, bs, zin + b0 * block_stride + size_t(r) * S, block_stride, S,
-                                  nb, st.stream)))
-                    return rc;
-        } else if (d2) {
+        if (d2) {  // only the k rows the plan reads cross PCIe
             for (int r : in_rows)
                 HIP_TRY(hipMemcpy2DAsync(st.d_in + size_t(r) * Sp, bs, h + size_t(r) * S, block_stride, S, nb,
                                          hipMemcpyHostToDevice, st.stream));
@@ -507,12 +498,7 @@ int reconstruct_host_impl(rsmi_ctx* c, uint8_t* shards, size_t block_stride, siz
                                       raw16 ? reinterpret_cast<uint32_t*>(c->d_crc) + b0 * n : nullptr,
                                       raw32 ? reinterpret_cast<uint32_t*>(c->d_crc32) + b0 * n : nullptr, st.stream)))
             return rc;
-        if (zc) {
-            for (int r : out_rows)
-                if ((rc = repitch(zc + b0 * block_stride + size_t(r) * S, block_stride, st.d_in + size_t(r) * Sp, bs, S,
-                                  nb, st.stream)))
-                    return rc;
-        } else if (d2) {
+        if (d2) {
             for (int r : out_rows)
                 HIP_TRY(hipMemcpy2DAsync(h + size_t(r) * S, block_stride, st.d_in + size_t(r) * Sp, bs, S, nb,
                                          hipMemcpyDeviceToHost, st.stream));
@@ -529,7 +515,7 @@ int reconstruct_host_impl(rsmi_ctx* c, uint8_t* shards, size_t block_stride, siz
     for (int s = 0; s < ns; s++) HIP_TRY(hipStreamSynchronize(c->staging[s].stream));
     if (raw16) HIP_TRY(hipMemcpy(raw16, c->d_crc, nblocks * n * 4, hipMemcpyDeviceToHost));
     if (raw32) HIP_TRY(hipMemcpy(raw32, c->d_crc32, nblocks * n * 4, hipMemcpyDeviceToHost));
-    if (!d2 && !zc) {
+    if (!d2) {
         for (size_t b0 = 0; b0 < nblocks; b0 += chunk) {
             const size_t nb = std::min(chunk, nblocks - b0);
             const uint8_t* hs = c->h_stage + b0 * nr * S;

@@ -396,11 +396,18 @@ class _HostBufs:
 @pytest.mark.parametrize("padded", [False, True])
 @pytest.mark.parametrize("memory", ["pageable", "pinned", "pinned-no-zero-copy", "pinned-zero-copy-2"])
 def test_batch_host_layouts(S, padded, memory):
-    """Host batch entry points over odd/even S and contiguous vs padded host block strides
-    (linear-copy + device repitch path for odd S, 2-D DMA path otherwise), from pageable
-    and page-locked host memory (results written back by kernel stores over PCIe)."""
+    """Host batch entry points over odd/even S and contiguous vs padded host block strides, with
+    every buffer of a case of one kind.  pageable and pinned-no-zero-copy: the copy-engine
+    pipeline where the call is above the small-call limit (linear copies + device repitch for odd
+    S, 2-D DMA otherwise), one chunk.  pinned and pinned-zero-copy-2: all buffers page-locked
+    with zero_copy on, so every call is the single zero-copy kernel in place over PCIe
+    (encode_small / reconstruct_small), whatever the value.  The pipeline past one chunk, and its
+    kernel write-back / kernel upload branches (page-locked memory on one side only), are
+    test_host_pipeline.py's."""
     bufs = _HostBufs(memory != "pageable")
     try:
+        # zero_copy 2 with everything page-locked still returns through the single zero-copy
+        # kernel; the upload-by-kernel branch it names needs pageable parity (test_host_pipeline.py)
         zc = {"pinned-no-zero-copy": 0, "pinned-zero-copy-2": 2}.get(memory, 1)
         _batch_host_layouts(S, padded, bufs, zc)
     finally:
