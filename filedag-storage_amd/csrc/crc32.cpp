@@ -110,11 +110,18 @@ Crc32Tables::Crc32Tables() {
     // A^-1 really inverts A, on a basis
     for (int bit = 0; bit < 32; bit++)
         if (apply(Q[0], apply(P[0], 1u << bit)) != (1u << bit)) std::abort();
+    // the group order shift() reduces by: A^(2^32 - 1) = I on a basis (every P[i] once)
+    for (int bit = 0; bit < 32; bit++) {
+        uint32_t s = 1u << bit;
+        for (int i = 0; i < kCrc32Powers; i++) s = apply(P[i], s);
+        if (s != (1u << bit)) std::abort();
+    }
 }
 
 uint32_t Crc32Tables::shift(uint32_t s, uint64_t n) const {
-    for (int i = 0; n && i < kCrc32Powers; i++, n >>= 1)
-        if (n & 1) s = apply(P[i], s);
+    uint32_t e = uint32_t(n % kCrc32Order);
+    for (int i = 0; e; i++, e >>= 1)
+        if (e & 1) s = apply(P[i], s);
     return s;
 }
 

@@ -6,12 +6,13 @@
 //   zero byte      A(s) = T[s & 0xFF] ^ (s >> 8)            (linear over GF(2), invertible)
 //   raw CRC        R(D) = fold of the byte update over D from s = 0
 //   Checksum(D)    = ~(A^|D|(0xFFFFFFFF) ^ R(D)),   R(D1 || D2) = A^|D2|(R(D1)) ^ R(D2)
-// No group order is used: forward shifts come from tables of A^(2^i), i < 32 (any 32-bit
-// byte count), backward ones (below 8 KiB: a row's last device segment ends up to 8191 bytes
-// past the row's end) from tables of A^-(2^i), i < 14.  The host applies them byte-sliced
-// (4 lookups).  The device folds with nibble tables (8 lookups per word, 16-entry tables that
-// never bank-conflict), and applies its few per-segment shifts in column form (a 32 x 32
-// matrix over GF(2) as the images of the 32 basis vectors: 2 VALU per bit, no lookups).
+// Forward shifts come from tables of A^(2^i), i < 32, with the byte count reduced by the group
+// order A^(2^32 - 1) = I (proved on a basis when the tables are built), so any 64-bit count is
+// right; backward ones (below 8 KiB: a row's last device segment ends up to 8191 bytes past the
+// row's end) come from tables of A^-(2^i), i < 14, not from the order.  The host applies them
+// byte-sliced (4 lookups).  The device folds with nibble tables (8 lookups per word, 16-entry
+// tables that never bank-conflict), and applies its few per-segment shifts in column form (a
+// 32 x 32 matrix over GF(2) as the images of the 32 basis vectors: 2 VALU per bit, no lookups).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -19,6 +20,7 @@
 namespace rsmi {
 
 constexpr int kCrc32Powers = 32;    // A^(2^i)
+constexpr uint64_t kCrc32Order = 0xFFFFFFFFull;  // A^(2^32 - 1) = I: shifts count modulo it
 constexpr int kCrc32InvPowers = 14;  // A^-(2^i): backward shifts up to 8192 bytes
 constexpr int kCrc32SegTiles = 8;    // device segment: 8 tiles of 1 KiB (rs_crc32_rows_kernel)
 constexpr int kCrc32ScanPowers = 6;  // A^(16 * 2^j), j < 6: the 64-lane scan of a tile
@@ -52,7 +54,7 @@ struct Crc32Tables {
     static uint32_t apply(const uint32_t (&t)[4][256], uint32_t s) {
         return t[0][s & 0xFF] ^ t[1][(s >> 8) & 0xFF] ^ t[2][(s >> 16) & 0xFF] ^ t[3][s >> 24];
     }
-    uint32_t shift(uint32_t s, uint64_t n) const;    // A^n(s), n < 2^32
+    uint32_t shift(uint32_t s, uint64_t n) const;    // A^n(s), any n (reduced modulo kCrc32Order)
     uint32_t unshift(uint32_t s, uint32_t n) const;  // A^-n(s), n < 8192
     // A^n / A^-n in column form (col[b] = image of 1 << b)
     void shift_columns(uint64_t n, uint32_t (&col)[32]) const;

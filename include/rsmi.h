@@ -280,7 +280,9 @@ uint32_t rsmi_crc32_ieee(const uint8_t* p, size_t n);
 
 /* ChecksumIEEE(head || D) from R32(D) and |D|: with head = the datanode entry's first 12 + meta
  * bytes (|crc16 (4 LE)|meta size|data size|meta|) this is the mutcask value checksum of a
- * shard D's entry.  head may be empty. */
+ * shard D's entry.  head may be empty.  Any data_len is accepted (the shift by |D| counts
+ * modulo 2^32 - 1, the order of the zero-byte step); only the device passes limit a row, to
+ * below 4 GiB. */
 uint32_t rsmi_crc32_entry(const uint8_t* head, size_t head_len, uint32_t raw, size_t data_len);
 
 /* R32(row) for nrows rows of S bytes per block on the device, laid out as in
