@@ -92,6 +92,16 @@ const FastKernelTable& fast_kernels();
 void* generic_kernel();
 void* repitch_kernel();
 
+// Encoder.Verify (rs_verify_kernels.hip): rs_verify_kernel per (K, MT), aligned and
+// unaligned-window layouts (null when K has no instantiation), and the compare of the fallback
+// (encode into scratch, then rs_compare_rows_kernel)
+struct VerifyKernelTable {
+    void* fn[17][kMaxMT + 1];
+    void* ua[17][kMaxMT + 1];
+};
+const VerifyKernelTable& verify_kernels();
+void* compare_rows_kernel();
+
 // CRC-16 of shard rows (crc16.hpp): the device table buffer holds P[15][2][256] (the powers
 // A^(2^i), byte-sliced) and N[32][16] (u16); a wave folds kCrcSegTiles 1 KiB tiles of one row
 // with one N lookup per nibble (16-entry tables: each wave-wide lookup touches 8 distinct

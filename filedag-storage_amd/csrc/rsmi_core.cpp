@@ -439,6 +439,10 @@ void rsmi_close(rsmi_ctx* c) {
             free_scratch(c->own_scratch);
             if (!c->stream_scratch.empty()) (void)hipDeviceSynchronize();  // caller streams may be gone
             for (auto& e : c->stream_scratch) free_scratch(e.second);
+            if (c->d_vbad) (void)hipFree(c->d_vbad);
+            if (!c->verify_scratch.empty()) (void)hipDeviceSynchronize();
+            for (auto& e : c->verify_scratch)
+                if (e.second.p) (void)hipFree(e.second.p);
             if (c->d_crc32_tbl) (void)hipFree(c->d_crc32_tbl);
             if (c->d_crc32) (void)hipFree(c->d_crc32);
         }

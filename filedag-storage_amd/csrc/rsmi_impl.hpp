@@ -3,8 +3,9 @@
 //   rsmi_host.cpp      host-memory calls: zero-copy single kernel, copy-engine pipeline
 //   rsmi_crc.cpp       datanode CRC-16 on the GPU (separate pass and fused into the encode)
 //   rsmi_coalesce.cpp  group commit of concurrent single-block calls
-// No CPU compute path anywhere: every byte of parity, reconstructed data or CRC comes out of
-// the HIP kernels in rs_kernels.hip.
+//   rsmi_verify.cpp    Encoder.Verify: stored parity checked against the data rows
+// No CPU compute path anywhere: every byte of parity, reconstructed data or CRC and every verify
+// flag comes out of the HIP kernels (rs_kernels.hip, rs_crc32_kernels.hip, rs_verify_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -132,6 +133,15 @@ struct rsmi_ctx {
     uint32_t* d_crc32_tbl = nullptr;  // CRC-32 device tables (crc32.hpp), uploaded on first use
     uint8_t* d_crc32 = nullptr;       // raw row CRC-32s of host batch calls
     size_t crc32_cap = 0;
+    // Encoder.Verify (rsmi_verify.cpp): the flags of host calls, and per stream the scratch its
+    // fallback encodes into (shapes without an rs_verify_kernel)
+    uint8_t* d_vbad = nullptr;
+    size_t vbad_cap = 0;
+    struct VerifyScratch {
+        uint8_t* p = nullptr;
+        size_t cap = 0;
+    };
+    std::map<hipStream_t, VerifyScratch> verify_scratch;
     rsmi::Crc32Shift crc32_shift{};  // launch_crc32's per-S shift matrix, for crc32_shift_S
     uint64_t crc32_shift_S = ~uint64_t(0);
     CrcScratch own_scratch;  // the fused encode + CRC-16's scratch on the context's own streams
@@ -251,6 +261,12 @@ int reconstruct_small(rsmi_ctx* c, const Plan& plan, uint8_t* shards, size_t bs,
 int reconstruct_host_impl(rsmi_ctx* c, uint8_t* shards, size_t block_stride, size_t S, size_t nblocks,
                                  const uint8_t* present, const uint8_t* want, uint32_t* raw16 = nullptr,
                           uint32_t* raw32 = nullptr);
+// Encoder.Verify of nblocks blocks (rsmi_verify.cpp; caller holds ctx->mu): bad[b*m + j], device
+// memory, zeroed here on the stream, then non-zero where stored parity row j of block b differs
+// from the encode of the block's data rows.  Stream-ordered, no synchronisation.
+int launch_verify(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
+                  const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks,
+                  uint32_t* bad, hipStream_t stream);
 int ensure_crc_tables(rsmi_ctx* c);
 int ensure_crc32_tables(rsmi_ctx* c);
 // R(row) / R32(row) of the rows the plan rebuilt (want && !present), one row per block at

@@ -1,0 +1,261 @@
+// rsmi_verify.cpp -- Encoder.Verify (include/rsmi.h rsmi_verify*; see rsmi_impl.hpp for the file
+// map): do the k + m shards of a block belong together, that is, is every stored parity row what
+// the encode of the data rows produces?  The check reads k + m rows and writes only flags:
+// rs_verify_kernel (rs_verify_kernels.hip) over the tiles of the cached encode plan, or, for
+// shapes it is not built for, the encode into scratch followed by rs_compare_rows_kernel.
+
+#include "rsmi_impl.hpp"
+
+#include <limits>
+
+using namespace rsmi;
+using namespace rsmi::impl;
+
+namespace rsmi {
+namespace impl {
+
+namespace {
+
+// The stream's scratch for the fallback's encoded rows (caller holds ctx->mu).  A caller that
+// cycles through many streams: past 32 of them the device is drained once and every stream's
+// scratch freed, as crc_scratch does.
+rsmi_ctx::VerifyScratch& verify_scratch(rsmi_ctx* c, hipStream_t st) {
+    auto it = c->verify_scratch.find(st);
+    if (it != c->verify_scratch.end()) return it->second;
+    if (c->verify_scratch.size() >= 32) {
+        (void)hipDeviceSynchronize();
+        for (auto& e : c->verify_scratch)
+            if (e.second.p) (void)hipFree(e.second.p);
+        c->verify_scratch.clear();
+    }
+    return c->verify_scratch[st];
+}
+
+}  // namespace
+
+int launch_verify(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
+                  const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks,
+                  uint32_t* bad, hipStream_t stream) {
+    if (nblocks == 0 || S == 0) return RSMI_OK;
+    const uint64_t m = uint64_t(c->m);
+    HIP_TRY(hipMemsetAsync(bad, 0, nblocks * m * sizeof(uint32_t), stream));
+    // the alignment test of launch_plan, the stored parity rows in the place of the output rows
+    const bool aligned = reinterpret_cast<uintptr_t>(data) % 16 == 0 && reinterpret_cast<uintptr_t>(parity) % 16 == 0 &&
+                         data_rs % 16 == 0 && data_bs % 16 == 0 && parity_rs % 16 == 0 && parity_bs % 16 == 0 &&
+                         data_rs >= round_up(S, 16) && parity_rs >= round_up(S, 16) && S < (uint64_t(1) << 31);
+    const bool ua = !aligned && S >= 16 && S < (uint64_t(1) << 31) && data_rs >= S && parity_rs >= S;
+    bool fast = aligned || ua;
+    for (const DevTile& t : plan.tiles)
+        if (t.K > 16 || !(aligned ? verify_kernels().fn : verify_kernels().ua)[t.K][t.MT]) fast = false;
+    if (fast) {
+        const uint64_t cpb = (S + 15) / 16;
+        const uint64_t tpb = (cpb + uint64_t(kWave) - 1) / uint64_t(kWave);
+        constexpr int wpg = kFastWG / kWave;
+        long wg_cap = std::numeric_limits<long>::max();
+        if (c->opt_waves_per_cu > 0) wg_cap = std::max(1L, long(c->num_cu) * c->opt_waves_per_cu / wpg);
+        // split into launches whose tile count fits 32 bits
+        const uint64_t max_blocks = std::max<uint64_t>(1, (uint64_t(1) << 31) / tpb);
+        std::string label;
+        for (const DevTile& t : plan.tiles) {
+            void* fn = (aligned ? verify_kernels().fn : verify_kernels().ua)[t.K][t.MT];
+            for (uint64_t b0 = 0; b0 < nblocks; b0 += max_blocks) {
+                const uint64_t nb = std::min(max_blocks, nblocks - b0);
+                uint32_t ntiles = uint32_t(nb * tpb);
+                uint32_t S32 = uint32_t(S), cpb32 = uint32_t(cpb), tpb32 = uint32_t(tpb), m32 = uint32_t(m);
+                const RsPlanDev* pd = t.dev;
+                const uint8_t* inb = data + b0 * data_bs;
+                const uint8_t* parb = parity + b0 * parity_bs;
+                uint32_t* badb = bad + b0 * m;
+                void* args[] = {&pd,  &inb,   &parb,  &data_bs, &data_rs, &parity_bs, &parity_rs,
+                                &S32, &cpb32, &tpb32, &ntiles,  &badb,    &m32};
+                const uint64_t wgs = std::min<uint64_t>((ntiles + wpg - 1) / wpg, uint64_t(wg_cap));
+                HIP_TRY(hipLaunchKernel(fn, dim3(uint32_t(wgs)), dim3(uint32_t(wpg * kWave)), args, 0, stream));
+            }
+            char buf[96];
+            std::snprintf(buf, sizeof buf, "rs_verify_kernel<K=%d,MT=%d>%s", t.K, t.MT, ua ? ",UA" : "");
+            label = buf;
+        }
+        set_last_kernel(c, label);
+        return hip_status(hipGetLastError());
+    }
+    // Shapes without an rs_verify_kernel (K > 16 or not instantiated, unaligned rows shorter than
+    // 16 bytes): the parity rows are encoded into scratch (16-byte-aligned rows, so the coding
+    // launch is whatever the data rows' layout allows) and compared with the stored ones,
+    // at most 64 MiB of scratch rows at a time.  The correctness path of rare shapes.
+    const uint64_t Sp = round_up(S, 16);
+    const uint64_t chunk = std::max<uint64_t>(1, (uint64_t(64) << 20) / (m * Sp));
+    rsmi_ctx::VerifyScratch& vs = verify_scratch(c, stream);
+    int rc = reserve_on(vs.p, vs.cap, std::min(chunk, nblocks) * m * Sp, stream);
+    if (rc) return rc;
+    for (uint64_t b0 = 0; b0 < nblocks; b0 += chunk) {
+        const uint64_t nb = std::min(chunk, nblocks - b0);
+        rc = launch_plan(c, plan, data + b0 * data_bs, data_rs, data_bs, vs.p, Sp, m * Sp, S, nb, stream);
+        if (rc) return rc;
+        const uint8_t* enc = vs.p;
+        const uint8_t* parb = parity + b0 * parity_bs;
+        uint64_t enc_bs = m * Sp, enc_rs = Sp, n = nb;
+        uint32_t m32 = uint32_t(m);
+        uint32_t* badb = bad + b0 * m;
+        const uint64_t groups = (S + 3) / 4;
+        const uint32_t gx = uint32_t(std::min<uint64_t>((groups + kWG - 1) / kWG, 4096));
+        const uint32_t gy = uint32_t(std::min<uint64_t>(nb, 65535));
+        void* args[] = {&enc, &enc_rs, &enc_bs, &parb, &parity_rs, &parity_bs, &S, &m32, &n, &badb};
+        HIP_TRY(hipLaunchKernel(compare_rows_kernel(), dim3(gx, gy), dim3(kWG), args, 0, stream));
+    }
+    set_last_kernel(c, "rs_compare_rows_kernel");
+    return hip_status(hipGetLastError());
+}
+
+namespace {
+
+// Host-memory verify.  Page-locked data and parity (and option zero_copy): one kernel reads them
+// in place over PCIe, rows at pitch S.  Small pageable calls: the same kernel over the context's
+// page-locked staging, filled by CPU copies (the rule of encode_small).  Everything else: chunks
+// of about 64 MiB of device rows round-robin over the staging streams, so a chunk's upload runs
+// while the chunk before it is checked; rows at rsmi_recommended_pitch(S) for the aligned
+// kernel, as the host encode stages them.  There is no write-back leg: only the flags return,
+// in one copy at the end.
+int verify_host_impl(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
+                     size_t parity_block_stride, size_t S, size_t nblocks, uint32_t* bad_out) {
+    if (!c || !data || !parity || !bad_out) return RSMI_ERR_INVALID_ARG;
+    if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
+    if (data_block_stride < size_t(c->k) * S || parity_block_stride < size_t(c->m) * S) return RSMI_ERR_INVALID_ARG;
+    if (nblocks == 0) return RSMI_OK;
+    std::lock_guard<std::mutex> g(c->mu);
+    int rc = ensure_device(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    std::shared_ptr<Plan> plan;
+    rc = encode_plan(c, plan);
+    if (rc) return rc;
+    const size_t k = size_t(c->k), m = size_t(c->m);
+    const size_t flag_bytes = nblocks * m * sizeof(uint32_t);
+    // the flags live in device memory on every path (no atomics aimed at host memory); every
+    // host call synchronises before it returns, so one buffer serves them all
+    if ((rc = reserve(c->d_vbad, c->vbad_cap, flag_bytes))) return rc;
+    uint32_t* d_bad = reinterpret_cast<uint32_t*>(c->d_vbad);
+
+    const size_t total = nblocks * (k + m) * S;
+    const size_t data_len = (nblocks - 1) * data_block_stride + k * S;
+    const size_t parity_len = (nblocks - 1) * parity_block_stride + m * S;
+    const uint8_t* zd = host_alias(const_cast<uint8_t*>(data), data_len);
+    const uint8_t* zp = host_alias(const_cast<uint8_t*>(parity), parity_len);
+    const bool pinned = zd && zp;
+    if ((c->opt_zero_copy && pinned) ||
+        (total <= size_t(c->opt_small_bytes) && (2 * total <= size_t(c->opt_small_bytes) || zd))) {
+        hipStream_t st = c->staging[0].stream;
+        size_t dbs = data_block_stride, pbs = parity_block_stride;
+        const size_t in_sz = zd ? 0 : nblocks * k * S, par_sz = zp ? 0 : nblocks * m * S;
+        if (in_sz + par_sz) {
+            uint8_t* hs = small_stage(c, in_sz + par_sz);
+            if (!hs) return RSMI_ERR_DEVICE;
+            if (!zd) {
+                for (size_t b = 0; b < nblocks; b++) std::memcpy(hs + b * k * S, data + b * data_block_stride, k * S);
+                zd = host_alias(hs, in_sz);
+                dbs = k * S;
+            }
+            if (!zp) {
+                for (size_t b = 0; b < nblocks; b++)
+                    std::memcpy(hs + in_sz + b * m * S, parity + b * parity_block_stride, m * S);
+                zp = host_alias(hs + in_sz, par_sz);
+                pbs = m * S;
+            }
+            if (!zd || !zp) return RSMI_ERR_DEVICE;
+        }
+        if ((rc = launch_verify(c, *plan, zd, S, dbs, zp, S, pbs, S, nblocks, d_bad, st))) return rc;
+        HIP_TRY(hipMemcpyAsync(bad_out, d_bad, flag_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return RSMI_OK;
+    }
+
+    const size_t Sp = rsmi_recommended_pitch(S);
+    const size_t in_bs = k * Sp, par_bs = m * Sp;
+    const bool d2 = dma_2d_ok(S);
+    const size_t chunk = std::max<size_t>(1, (size_t(64) << 20) / (in_bs + par_bs));
+    const int ns = nblocks > chunk ? 3 : 1;
+    // odd S: the PCIe copies stay linear (d_lin, data rows then parity rows in stream order) and
+    // rs_repitch_kernel lays the rows out at the device pitch (rsmi_host.cpp)
+    auto upload = [&](Staging& st, uint8_t* dst, size_t dst_bs, const uint8_t* src, size_t src_bs, size_t rows,
+                      size_t nb) -> int {
+        if (d2 && src_bs == rows * S) {
+            HIP_TRY(hipMemcpy2DAsync(dst, Sp, src, S, S, nb * rows, hipMemcpyHostToDevice, st.stream));
+        } else if (d2) {
+            for (size_t b = 0; b < nb; b++)
+                HIP_TRY(hipMemcpy2DAsync(dst + b * dst_bs, Sp, src + b * src_bs, S, S, rows, hipMemcpyHostToDevice,
+                                         st.stream));
+        } else {
+            if (src_bs == rows * S)
+                HIP_TRY(hipMemcpyAsync(st.d_lin, src, nb * rows * S, hipMemcpyHostToDevice, st.stream));
+            else
+                for (size_t b = 0; b < nb; b++)
+                    HIP_TRY(hipMemcpyAsync(st.d_lin + b * rows * S, src + b * src_bs, rows * S, hipMemcpyHostToDevice,
+                                           st.stream));
+            return repitch(dst, Sp, st.d_lin, S, S, nb * rows, st.stream);
+        }
+        return RSMI_OK;
+    };
+    for (size_t b0 = 0, i = 0; b0 < nblocks; b0 += chunk, i++) {
+        Staging& st = c->staging[i % ns];
+        const size_t nb = std::min(chunk, nblocks - b0);
+        if ((rc = reserve_on(st.d_in, st.in_cap, nb * in_bs, st.stream))) return rc;
+        if ((rc = reserve_on(st.d_out, st.out_cap, nb * par_bs, st.stream))) return rc;
+        if (!d2 && (rc = reserve_on(st.d_lin, st.lin_cap, nb * std::max(k, m) * S, st.stream))) return rc;
+        if ((rc = upload(st, st.d_in, in_bs, data + b0 * data_block_stride, data_block_stride, k, nb))) return rc;
+        if ((rc = upload(st, st.d_out, par_bs, parity + b0 * parity_block_stride, parity_block_stride, m, nb)))
+            return rc;
+        if ((rc = launch_verify(c, *plan, st.d_in, Sp, in_bs, st.d_out, Sp, par_bs, S, nb, d_bad + b0 * m, st.stream)))
+            return rc;
+    }
+    for (int s = 0; s < ns; s++) HIP_TRY(hipStreamSynchronize(c->staging[s].stream));
+    HIP_TRY(hipMemcpy(bad_out, d_bad, flag_bytes, hipMemcpyDeviceToHost));
+    return RSMI_OK;
+}
+
+}  // namespace
+
+}  // namespace impl
+}  // namespace rsmi
+
+extern "C" {
+
+int rsmi_verify_batch_dev(rsmi_ctx* c, const uint8_t* d_data, size_t data_shard_stride, size_t data_block_stride,
+                          const uint8_t* d_parity, size_t parity_shard_stride, size_t parity_block_stride, size_t S,
+                          size_t nblocks, uint32_t* d_bad_out, void* stream) try {
+    if (!c || !d_data || !d_parity || !d_bad_out) return RSMI_ERR_INVALID_ARG;
+    if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
+    if (data_shard_stride < S || parity_shard_stride < S) return RSMI_ERR_INVALID_ARG;
+    if (nblocks == 0) return RSMI_OK;
+    std::shared_ptr<Plan> plan;
+    std::lock_guard<std::mutex> g(c->mu);
+    int rc = ensure_device(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    rc = encode_plan(c, plan);
+    if (rc) return rc;
+    return launch_verify(c, *plan, d_data, data_shard_stride, data_block_stride, d_parity, parity_shard_stride,
+                         parity_block_stride, S, nblocks, d_bad_out, static_cast<hipStream_t>(stream));
+} catch (...) {
+    return rsmi::impl::exception_status();
+}
+
+int rsmi_verify_batch_host(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
+                           size_t parity_block_stride, size_t S, size_t nblocks, uint32_t* bad_out) try {
+    return verify_host_impl(c, data, data_block_stride, parity, parity_block_stride, S, nblocks, bad_out);
+} catch (...) {
+    return rsmi::impl::exception_status();
+}
+
+int rsmi_verify(rsmi_ctx* c, const uint8_t* shards, size_t S, int* ok_out) try {
+    if (!c || !shards || !ok_out) return RSMI_ERR_INVALID_ARG;
+    if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
+    const size_t k = size_t(c->k), m = size_t(c->m);
+    std::vector<uint32_t> bad(m, 0);
+    int rc = verify_host_impl(c, shards, k * S, shards + k * S, m * S, S, 1, bad.data());
+    if (rc) return rc;
+    *ok_out = std::all_of(bad.begin(), bad.end(), [](uint32_t x) { return x == 0; }) ? 1 : 0;
+    return RSMI_OK;
+} catch (...) {
+    return rsmi::impl::exception_status();
+}
+
+}  // extern "C"

@@ -82,6 +82,11 @@ def lib() -> ctypes.CDLL:
         "rsmi_host_free": (None, [ctypes.c_void_p]),
         "rsmi_encode_batch_dev": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, u8p, c_size, c_size, c_size, c_size, ctypes.c_void_p]),
         "rsmi_reconstruct_batch_dev": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, c_size, c_size, u8p, ctypes.c_int, ctypes.c_void_p]),
+        "rsmi_verify_batch_dev": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, u8p, c_size, c_size, c_size, c_size,
+                                                 ctypes.c_void_p, ctypes.c_void_p]),
+        "rsmi_verify_batch_host": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, u8p, c_size, c_size, c_size,
+                                                  ctypes.c_void_p]),
+        "rsmi_verify": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, ctypes.POINTER(ctypes.c_int)]),
         "rsmi_encode_block_coalesced": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, u8p, ctypes.c_void_p]),
         "rsmi_encode_block_coalesced_crcs": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, u8p, ctypes.c_void_p,
                                                             ctypes.c_void_p]),
@@ -243,6 +248,20 @@ class Codec:
                               nblocks: int) -> None:
         _check(lib().rsmi_encode_batch_host(self._h, data_ptr, data_bs, parity_ptr, parity_bs, S, nblocks))
 
+    def verify(self, shards, S: int) -> bool:
+        """Encoder.Verify of one block of n*S contiguous bytes: True iff every parity row is the
+        encode of the data rows (rsmi_verify)."""
+        src = shards if isinstance(shards, bytearray) else bytearray(shards)
+        ok = ctypes.c_int(-1)
+        _check(lib().rsmi_verify(self._h, ctypes.addressof(_buf(src)) if src else None, S, ctypes.byref(ok)))
+        return ok.value == 1
+
+    def verify_batch_host_ptr(self, data_ptr: int, data_bs: int, parity_ptr: int, parity_bs: int, S: int,
+                              nblocks: int, bad_ptr: int) -> None:
+        """rsmi_verify_batch_host: bad_ptr[b*m + j] (uint32, host memory) non-zero iff parity row j
+        of block b differs from the encode of the block's data rows."""
+        _check(lib().rsmi_verify_batch_host(self._h, data_ptr, data_bs, parity_ptr, parity_bs, S, nblocks, bad_ptr))
+
     def reconstruct_batch_host_ptr(self, ptr: int, bs: int, S: int, nblocks: int, present: Sequence[bool],
                                    data_only: bool) -> None:
         p = bytearray(1 if x else 0 for x in present)
@@ -338,6 +357,13 @@ class Codec:
                          parity_bs: int, S: int, nblocks: int, stream: int = 0) -> None:
         _check(lib().rsmi_encode_batch_dev(self._h, d_data, data_rs, data_bs, d_parity, parity_rs, parity_bs, S,
                                            nblocks, stream or None))
+
+    def verify_batch_dev(self, d_data: int, data_rs: int, data_bs: int, d_parity: int, parity_rs: int,
+                         parity_bs: int, S: int, nblocks: int, d_bad: int, stream: int = 0) -> None:
+        """rsmi_verify_batch_dev: d_bad[b*m + j] (uint32, device memory, zeroed on the stream first)
+        non-zero iff stored parity row j of block b is not the encode of the block's data rows."""
+        _check(lib().rsmi_verify_batch_dev(self._h, d_data, data_rs, data_bs, d_parity, parity_rs, parity_bs, S,
+                                           nblocks, d_bad, stream or None))
 
     def reconstruct_rows_batch_dev(self, d_shards: int, rs: int, bs: int, S: int, nblocks: int,
                                    present: Sequence[bool], required: Sequence[bool], stream: int = 0) -> None:
@@ -535,6 +561,18 @@ class Erasure:
     def decode_data_and_parity_blocks(self, data: List[Optional[bytes]]) -> None:
         """erasure.go:87-93 DecodeDataAndParityBlocks -> Reconstruct."""
         self._reconstruct(data, data_only=False)
+
+    def verify(self, shards: List[bytes]) -> bool:
+        """Encoder.Verify (not called by erasure.go; offered for scrubs): True iff the parity
+        shards are the encode of the data shards.  Upstream's checks come first: a shard list of
+        the wrong length is ErrTooFewShards, and checkShards with nilok = false rejects empty
+        lists (ErrShardNoData) and missing or unequal shards (ErrShardSize)."""
+        n = self.data_blocks + self.parity_blocks
+        if len(shards) != n:
+            raise RsmiError(ErrTooFewShards)  # upstream: len(shards) != totalShards
+        rc, S = check_shards([len(s) if s else 0 for s in shards], nil_ok=False)
+        _check(rc)
+        return self.encoder().verify(bytearray(b"".join(shards)), S)
 
 
 def NewErasure(data_blocks: int, parity_blocks: int, block_size: int, device: int = 0) -> Erasure:

@@ -34,7 +34,8 @@ extern "C" {
  * 4: coalesced calls run on up to "coalesce_lanes" batches at once (new option, default 2);
  * rsmi_warm is new; the device-resident CRC entry points may run concurrently on different streams
  * of one context; rsmi_last_kernel returns a per-thread copy.
- * 5: the per-thread wait hook (rsmi_set_wait_hook, rsmi_run_wait_hook). */
+ * 5: the per-thread wait hook (rsmi_set_wait_hook, rsmi_run_wait_hook).  The Encoder.Verify entry
+ * points (rsmi_verify, rsmi_verify_batch_host, rsmi_verify_batch_dev) joined version 5: additive. */
 #define RSMI_ABI_VERSION 5
 
 typedef struct rsmi_ctx rsmi_ctx;
@@ -158,6 +159,32 @@ int rsmi_reconstruct_batch_dev(rsmi_ctx* ctx, uint8_t* d_shards, size_t shard_st
 int rsmi_reconstruct_rows_batch_dev(rsmi_ctx* ctx, uint8_t* d_shards, size_t shard_stride, size_t block_stride,
                                     size_t S, size_t nblocks, const uint8_t* present, const uint8_t* required,
                                     void* stream);
+
+/* ------------------------------------------------------------------ Encoder.Verify */
+
+/* Do the k+m shards of a block belong together: is every parity row what Encode would produce
+ * from the data rows?  The Dag Node never calls Verify; it is offered for scrubs of stored
+ * stripes and for confirming a repair or a migration before the old copy is dropped.  A shard
+ * checksum says a shard is the bytes that were stored; only this check says it is the right
+ * shard for the stripe (not stale, swapped between keys, or rebuilt from a bad survivor).  The
+ * check reads k+m rows and writes only flags; bytes outside a row (padding) never count.  None of
+ * these calls takes or clears the per-thread wait hook. */
+
+/* Encoder.Verify, device-resident: layout as rsmi_encode_batch_dev; nothing is written but
+ * d_bad_out[b*m + j] (device memory, nblocks*m words, zeroed first on the stream), non-zero iff
+ * parity row j of block b differs from the encode of its data rows.  Stream-ordered, no sync. */
+int rsmi_verify_batch_dev(rsmi_ctx* ctx, const uint8_t* d_data, size_t data_shard_stride, size_t data_block_stride,
+                          const uint8_t* d_parity, size_t parity_shard_stride, size_t parity_block_stride,
+                          size_t S, size_t nblocks, uint32_t* d_bad_out, void* stream);
+
+/* Host memory, layout as rsmi_encode_batch_host; bad_out[b*m + j] in host memory.  Page-locked
+ * data and parity (rsmi_host_alloc) are read in place over PCIe by one kernel; small pageable
+ * calls are staged by CPU copies; larger ones are uploaded in chunks that overlap the check. */
+int rsmi_verify_batch_host(rsmi_ctx* ctx, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
+                           size_t parity_block_stride, size_t S, size_t nblocks, uint32_t* bad_out);
+
+/* Encoder.Verify of one block: n*S contiguous bytes; *ok_out = 1 iff every parity row matches. */
+int rsmi_verify(rsmi_ctx* ctx, const uint8_t* shards, size_t S, int* ok_out);
 
 /* Erasure.EncodeData for one block (same output as rsmi_encode_block, plus R(shard) in
  * raw_out[0..k+m) when raw_out is not NULL), coalesced with concurrent callers on the same
