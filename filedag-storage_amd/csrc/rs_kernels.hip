@@ -134,7 +134,8 @@ __global__ __launch_bounds__(kFastWG, WPS) void rs_fast_kernel(const RsPlanDev* 
                                                        const uint8_t* __restrict__ in, uint8_t* __restrict__ out,
                                                        uint64_t in_bs, uint64_t in_rs, uint64_t out_bs,
                                                        uint64_t out_rs, uint32_t S, uint32_t cpb, uint32_t tpb,
-                                                       uint32_t ntiles, const uint32_t* __restrict__ crc_tbl,
+                                                       uint32_t ntiles, uint32_t head,
+                                                       const uint32_t* __restrict__ crc_tbl,
                                                        uint32_t* __restrict__ crc_rec, uint32_t* __restrict__ crc_tail,
                                                        BasesArg<TB> bases) {
     static_assert(NT == 1 || NT == 2, "cache policy 1 or 2");
@@ -175,14 +176,15 @@ __global__ __launch_bounds__(kFastWG, WPS) void rs_fast_kernel(const RsPlanDev* 
     const uint32_t lane = threadIdx.x & (kWave - 1);
     const uint32_t wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const uint32_t nw = gridDim.x * kWavesPerWG;
-    // UA: workgroups renumbered so each XCD (the dispatcher deals workgroups round-robin over
-    // the 8 XCDs) takes one contiguous eighth of the tiles.  A row's 1 KiB tile at an odd address
-    // shares its first and last 64-byte lines with the neighbouring tiles; with the neighbours on
-    // the same XCD those lines come from one L2 (Split layout: encode +4-5%).
-    // Aligned layouts share no lines and keep the plain order (re-measured in round 2: +1.2% on
-    // RS(10,4) 256 KiB, -1.3 to -3% on the other BASELINE shapes, profiles/r02/cfg_ab_xcd.txt).
-    uint32_t wg = blockIdx.x;
-    if (UA && (gridDim.x & 7u) == 0u) wg = (wg & 7u) * (gridDim.x >> 3) + (wg >> 3);
+    // The first head workgroups are renumbered so each XCD (the dispatcher deals workgroups
+    // round-robin over the 8 XCDs) sweeps one contiguous range of tiles; the rest keep the plain
+    // order (tile_group, rs_plan.hpp; head chosen by launch_head).  UA: a row's 1 KiB tile at an
+    // odd address shares its first and last 64-byte lines with the neighbouring tiles; with the
+    // neighbours on the same XCD those lines come from one L2 (Split layout: encode +4-5%,
+    // DESIGN.md §3), so head is the whole grid.  Aligned layouts share no lines: only the shapes
+    // of tile_group_shape are ever passed a head, the others keep blockIdx.x.
+    const uint32_t wg =
+        (UA || tile_group_shape(K, MT)) ? tile_group(blockIdx.x, gridDim.x, head) : uint32_t(blockIdx.x);
     uint32_t t = wg * kWavesPerWG + wid;
     if constexpr (TB) {
         // a table launch may release a completion flag (launch_done, as every workgroup's last

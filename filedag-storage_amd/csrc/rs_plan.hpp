@@ -34,6 +34,51 @@ constexpr int kMinWavesPerSimd = 4;  // caps the fast kernels at 128 VGPRs (16 w
 #define RSMI_UA_NT_LOADS 1
 #endif
 
+#if defined(__HIPCC__)
+#define RSMI_HOST_DEVICE __host__ __device__
+#else
+#define RSMI_HOST_DEVICE
+#endif
+// Workgroup -> tile group of the coding kernels (launch geometry).  The dispatcher
+// deals workgroups round-robin over the 8 XCDs, so workgroup wg lands on XCD wg & 7 (observed,
+// not promised: the mapping is for speed only and a bijection of [0, grid) whatever the placement).
+// The first head workgroups (head a multiple of 8, head <= grid) are renumbered so that each XCD
+// sweeps one contiguous range of head / 8 tile groups; the rest keep the plain order, which leaves
+// the launch's tail to the dispatcher's balancing.  head = 0: the plain order.
+RSMI_HOST_DEVICE inline uint32_t tile_group(uint32_t wg, uint32_t grid, uint32_t head) {
+    (void)grid;
+    return wg < head ? (wg & 7u) * (head >> 3) + (wg >> 3) : wg;
+}
+// The share of an aligned launch's workgroups that is grouped: num / den of the grid for the
+// shapes of the table below, none for every other.  Of 1, 15/16, 7/8 and 3/4 the whole grid was
+// best on the one shape that gains (profiles/xcd_tail/ab.txt).
+struct TileGroupShare {
+    uint32_t num, den;
+};
+constexpr TileGroupShare kTileGroupShare = {1, 1};
+// Per tile shape (K, MT) and row size S, beside auto_cache_policy (rsmi_core.cpp): measured on the
+// BASELINE shapes.  RS(10,4) rows of 256 KiB blocks (S = 26 215, 26 tiles a row) gain about 1.2 %,
+// encode (MT = 4) and one-row reconstruct (MT = 1) alike; the same K with 1 MiB blocks
+// (S = 104 858) loses 1.3 %, RS(4,2), RS(16,4) and RS(2,1) lose 0.4-3.5 % at every share.  Shapes
+// that were not measured keep the plain order.
+// The aligned kernels of the other (K, MT) leave the mapping out at compile time (rs_fast_kernel),
+// so their code stays what it was.
+constexpr bool tile_group_shape(int K, int MT) { return K == 10 && (MT == 4 || MT == 1); }
+inline TileGroupShare tile_group_share(int K, int MT, uint32_t S) {
+    if (tile_group_shape(K, MT) && S <= 32768u) return kTileGroupShare;
+    return {0, 1};
+}
+// head of a coding launch (launch_plan) of grid workgroups.  Unaligned-window layouts (ua): the
+// whole grid when it is a multiple of 8, else none (neighbouring tiles share cache lines there,
+// DESIGN.md §3).  A grid capped by waves_per_cu (strided: each wave loops over further tiles)
+// keeps the plain order.
+inline uint32_t launch_head(uint32_t grid, int K, int MT, uint32_t S, bool ua, bool strided) {
+    if (ua) return (grid & 7u) == 0u ? grid : 0u;
+    if (strided) return 0u;
+    const TileGroupShare s = tile_group_share(K, MT, S);
+    return uint32_t(uint64_t(grid) * s.num / s.den) & ~7u;
+}
+
 // One launch tile: MT (<= 4) output rows computed from K input rows.
 // tbl[c*20 + f*4 + j] = field-f product word for coefficient coef[j][c] (gf256.hpp
 // perm_tables); padded outputs (j >= MT) have all-zero tables.

@@ -222,6 +222,8 @@ const char* kernel_label(int K, int MT, int NT, bool fast) {
 // once the tile reads at least 4 rows per row written (RS(10,4) 1-row reconstruct -5 %,
 // 2-row -3 %, RS(16,4) 2-row -4 %, RS(4,2) 1-row -5 %; RS(16,4) encode is a tie).
 int auto_cache_policy(int K, int MT) { return K >= 4 * MT ? 2 : 1; }
+// The other per-shape choice of a launch, its tile order across XCDs, is tile_group_share /
+// launch_head in rs_plan.hpp (there so that the kernels and the host test share it).
 
 uintptr_t table_alignment(const BlockBases* tb, uint64_t nblocks) {
     uintptr_t a = 0;
@@ -294,9 +296,13 @@ int launch_plan(rsmi_ctx* c, const Plan& plan, const uint8_t* in, uint64_t in_rs
                     if (armed) *armed = tbl_args.done_flag != nullptr;
                 }
                 void* bases = tb ? static_cast<void*>(&tbl_args) : static_cast<void*>(&nob);
+                const uint64_t all_wgs = (uint64_t(ntiles) + wpg - 1) / wpg;
+                const uint64_t wgs = std::min<uint64_t>(all_wgs, uint64_t(wg_cap));
+                // the workgroups renumbered into per-XCD contiguous tile ranges (tile_group); the
+                // aligned CRC forms were not part of the measurement and keep the plain order
+                uint32_t head = launch_head(uint32_t(wgs), t.K, t.MT, S32, !aligned, wgs < all_wgs || fuse != nullptr);
                 void* args[] = {&pd,    &inb,   &outb,   &in_bs, &in_rs, &out_bs, &out_rs, &S32,
-                                &cpb32, &tpb32, &ntiles, &ctbl,  &crec,  &ctail, bases};
-                const uint64_t wgs = std::min<uint64_t>((ntiles + wpg - 1) / wpg, uint64_t(wg_cap));
+                                &cpb32, &tpb32, &ntiles, &head,  &ctbl,  &crec,   &ctail,  bases};
                 HIP_TRY(hipLaunchKernel(fn, dim3(uint32_t(wgs)), dim3(uint32_t(wpg * kWave)), args, 0, stream));
             }
             std::string label = kernel_label(t.K, t.MT, NT, true);
