@@ -126,10 +126,14 @@ __device__ __forceinline__ void launch_done(const BasesArg<TB>& bases) {
 // when the caller caps the grid (option waves_per_cu).
 // TB: the blocks lie where a table of block bases says (BlockBases: a coalesced group of callers'
 // own page-locked buffers, one launch for the group); in / out are offsets from each base.
+// ST: how the aligned form stores its output rows (store_policy, rs_plan.hpp): 0 plain, 1
+// nontemporal, n >= 2 nontemporal but the last n - 1 rows plain.  The default is what NT says, and
+// the launch label prints NT alone.
 #ifndef RSMI_ROWS_FIRST  // 1: the coding table staged after the first rows are issued (A/B)
 #define RSMI_ROWS_FIRST 0
 #endif
-template <int K, int MT, int NT, int WPS = kMinWavesPerSimd, bool UA = false, bool CRC = false, bool TB = false>
+template <int K, int MT, int NT, int WPS = kMinWavesPerSimd, bool UA = false, bool CRC = false, bool TB = false,
+          int ST = (NT == 1 ? 1 : 0)>
 __global__ __launch_bounds__(kFastWG, WPS) void rs_fast_kernel(const RsPlanDev* __restrict__ plan,
                                                        const uint8_t* __restrict__ in, uint8_t* __restrict__ out,
                                                        uint64_t in_bs, uint64_t in_rs, uint64_t out_bs,
@@ -139,6 +143,7 @@ __global__ __launch_bounds__(kFastWG, WPS) void rs_fast_kernel(const RsPlanDev* 
                                                        uint32_t* __restrict__ crc_rec, uint32_t* __restrict__ crc_tail,
                                                        BasesArg<TB> bases) {
     static_assert(NT == 1 || NT == 2, "cache policy 1 or 2");
+    static_assert(ST >= 0 && ST <= MT, "store policy 0, 1, or 2..MT: the last ST - 1 rows plain");
     constexpr int NSH = K + MT;            // CRC: shards of the block (encode plans)
     constexpr int NSL = (NSH + 3) / 4;     // CRC: rows each lane keeps (r = q mod 4)
     __shared__ u32x4 s_tbl[K * kColDwords / 4];
@@ -416,7 +421,9 @@ __global__ __launch_bounds__(kFastWG, WPS) void rs_fast_kernel(const RsPlanDev* 
 #pragma unroll
                 for (int j = 0; j < MT; j++) {
                     const u32x4 o = u32x4{acc[j][0], acc[j][1], acc[j][2], acc[j][3]};
-                    if constexpr (NT == 1)
+                    if constexpr (ST == 1)
+                        __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(ob + out_off[j]) + ch);
+                    else if (ST >= 2 && j + (ST - 1) < MT)  // a constant once the row loop is unrolled
                         __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(ob + out_off[j]) + ch);
                     else
                         *(reinterpret_cast<u32x4*>(ob + out_off[j]) + ch) = o;
@@ -1533,7 +1540,8 @@ void* crc16_rows_kernel(bool aligned) {
 
 // ------------------------------------------------------------------ dispatch table
 // One kernel per (K, MT) and layout, with the cache policy of the shape (auto_cache_policy in
-// rsmi_core.cpp): nontemporal stores unless the tile reads at least 4 rows per row it writes.
+// rsmi_core.cpp): nontemporal stores unless the tile reads at least 4 rows per row it writes
+// (the rows of the grouped tile order: store_policy, rs_plan.hpp).
 constexpr int auto_nt(int K, int MT) { return K >= 4 * MT ? 2 : 1; }
 constexpr int ua_nt(int K, int MT) { return RSMI_UA_NT ? RSMI_UA_NT : auto_nt(K, MT); }
 
@@ -1593,6 +1601,10 @@ template <int K, int MT>
 static void fill_km(FastKernelTable& t) {
     constexpr int NT = auto_nt(K, MT);
     t.fn[K][MT] = reinterpret_cast<void*>(&rs_fast_kernel<K, MT, NT>);
+    // the rows of the grouped order store by the shape's own policy (store_policy, rs_plan.hpp)
+    if constexpr (store_policy_shape(K, MT, NT))
+        t.fn_sp[K][MT] = reinterpret_cast<void*>(
+            &rs_fast_kernel<K, MT, NT, kMinWavesPerSimd, false, false, false, store_policy(K, MT, NT)>);
     t.ua[K][MT] = reinterpret_cast<void*>(&rs_fast_kernel<K, MT, ua_nt(K, MT), kMinWavesPerSimd, true>);
     t.crc[K][MT] = reinterpret_cast<void*>(&rs_fast_kernel<K, MT, NT, kMinWavesPerSimd, false, true>);
     t.ua_crc[K][MT] = reinterpret_cast<void*>(&rs_fast_kernel<K, MT, NT, kMinWavesPerSimd, true, true>);

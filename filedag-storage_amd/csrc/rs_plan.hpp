@@ -64,9 +64,29 @@ constexpr TileGroupShare kTileGroupShare = {1, 1};
 // The aligned kernels of the other (K, MT) leave the mapping out at compile time (rs_fast_kernel),
 // so their code stays what it was.
 constexpr bool tile_group_shape(int K, int MT) { return K == 10 && (MT == 4 || MT == 1); }
+constexpr uint32_t kGroupedRowMax = 32768u;  // ... with rows of at most this many bytes
 inline TileGroupShare tile_group_share(int K, int MT, uint32_t S) {
-    if (tile_group_shape(K, MT) && S <= 32768u) return kTileGroupShare;
+    if (tile_group_shape(K, MT) && S <= kGroupedRowMax) return kTileGroupShare;
     return {0, 1};
+}
+// How the plain aligned coding kernel (rs_fast_kernel without UA, CRC or TB) stores its output
+// rows on the rows that take the grouped order, beside the cache policy NT (auto_cache_policy,
+// rsmi_core.cpp), which keeps naming the loads and the launch label:
+//   0  plain stores            1  nontemporal stores
+//   n >= 2  nontemporal stores, but the last n - 1 output rows plain
+// Measured under the grouped order on the two shapes that take it (profiles/store_path/ab.txt,
+// DESIGN.md §4.1): the RS(10,4) encode with its last parity row stored plain is 3.9 % faster than
+// with all four nontemporal (all plain -4.6 %, two plain rows slow the launch that follows); the
+// one-row reconstruct keeps its plain stores (nontemporal -5.8 %).  Every other shape, and longer
+// rows of these, keep what the cache policy says and the kernel they had (FastKernelTable::fn).
+constexpr int store_policy(int K, int MT, int NT) {
+    if (K == 10 && MT == 4) return 2;
+    return NT == 1 ? 1 : 0;
+}
+// a shape whose policy on those rows differs from its cache policy's has a kernel of its own for
+// them (FastKernelTable::fn_sp)
+constexpr bool store_policy_shape(int K, int MT, int NT) {
+    return tile_group_shape(K, MT) && store_policy(K, MT, NT) != (NT == 1 ? 1 : 0);
 }
 // head of a coding launch (launch_plan) of grid workgroups.  Unaligned-window layouts (ua): the
 // whole grid when it is a multiple of 8, else none (neighbouring tiles share cache lines there,
@@ -115,6 +135,7 @@ using BasesArg = std::conditional_t<TB, BlockBases, NoBases>;
 // of every row fused in (encode plans).
 struct FastKernelTable {
     void* fn[17][kMaxMT + 1];
+    void* fn_sp[17][kMaxMT + 1];  // aligned rows up to kGroupedRowMax of a store_policy_shape (null: fn)
     void* ua[17][kMaxMT + 1];
     void* crc[17][kMaxMT + 1];
     void* ua_crc[17][kMaxMT + 1];

@@ -222,8 +222,10 @@ const char* kernel_label(int K, int MT, int NT, bool fast) {
 // once the tile reads at least 4 rows per row written (RS(10,4) 1-row reconstruct -5 %,
 // 2-row -3 %, RS(16,4) 2-row -4 %, RS(4,2) 1-row -5 %; RS(16,4) encode is a tie).
 int auto_cache_policy(int K, int MT) { return K >= 4 * MT ? 2 : 1; }
-// The other per-shape choice of a launch, its tile order across XCDs, is tile_group_share /
-// launch_head in rs_plan.hpp (there so that the kernels and the host test share it).
+// The other per-shape choices of a launch are in rs_plan.hpp (there so that the kernels and the
+// host test share them): its tile order across XCDs, tile_group_share / launch_head, and, on the
+// rows that order takes, how the output rows are stored, store_policy, re-measured under that order
+// (RS(10,4) encode: the last parity row plain, +3.9 %; profiles/store_path/ab.txt).
 
 uintptr_t table_alignment(const BlockBases* tb, uint64_t nblocks) {
     uintptr_t a = 0;
@@ -260,6 +262,11 @@ int launch_plan(rsmi_ctx* c, const Plan& plan, const uint8_t* in, uint64_t in_rs
             else if (fuse) fn = ua ? fast_kernels().ua_crc[t.K][t.MT] : fast_kernels().crc[t.K][t.MT];
             else if (aligned) fn = fast_kernels().fn[t.K][t.MT];
             else if (ua) fn = fast_kernels().ua[t.K][t.MT];
+            // the third per-shape choice, how the output rows are stored (store_policy,
+            // rs_plan.hpp): the plain aligned launch of a row the grouped order takes runs the
+            // shape's own kernel where it has one; the label stays the cache policy's
+            if (aligned && !tb && !fuse && S <= kGroupedRowMax && fast_kernels().fn_sp[t.K][t.MT])
+                fn = fast_kernels().fn_sp[t.K][t.MT];
         }
         if (fuse && !fn) return RSMI_ERR_INVALID_ARG;
         if (fn) {
