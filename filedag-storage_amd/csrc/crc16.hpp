@@ -12,7 +12,7 @@
 // A is invertible with A^32767 = I (x^16+x^15+x^2+1 = (x+1)(x^15+x+1), x^15+x+1 primitive),
 // so shifts by negative byte counts are shifts by (n mod 32767).
 //
-// Device split (rs_kernels.hip rs_crc16_rows_kernel): each lane folds 16-byte chunks with
+// Device split (rs_crc16_kernels.hip rs_crc16_rows_kernel): each lane folds 16-byte chunks with
 // positional tables -- R(chunk) = XOR_p U[15-p][b_p], U[p][b] = A^p(T[b]), or by linearity
 // the same with one lookup per nibble in 16-entry tables N -- lanes and tiles
 // combine with the power tables A^(2^i), and one atomic XOR per (row, segment) lands the

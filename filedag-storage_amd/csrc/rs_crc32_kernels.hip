@@ -1,6 +1,6 @@
 // rs_crc32_kernels.hip -- R(row) of shard rows for the mutcask value checksum (CRC-32 IEEE,
 // kv/mutcask/cask.go:73-97; algebra in crc32.hpp), the CRC-32 sibling of
-// rs_crc16_rows_kernel (rs_kernels.hip).
+// rs_crc16_rows_kernel (rs_crc16_kernels.hip).
 //
 // Work item = (row, up to kCrc32SupGroups segments of kCrc32SegTiles = 8 consecutive 1 KiB
 // tiles).  Each lane loads its 16-byte chunk of every tile of a segment and folds each
@@ -230,15 +230,13 @@ __global__ __launch_bounds__(kWG) void rs_crc32_rows_pipe_kernel(const uint32_t*
                     const int64_t valid = int64_t(Sm) - int64_t((uint64_t(t0 + i) * kWave + lane) * 16);
 #pragma unroll
                     for (int w = 0; w < 4; w++) {
-                        const int64_t n = valid - 4 * w;
-                        v[i][w] &= n >= 4 ? ~0u : n <= 0 ? 0u : (1u << (8 * n)) - 1u;
+                        v[i][w] &= bytes_mask(valid - 4 * w);
                     }
                 }
                 if (UA && t0 + i == 0 && mis != 0u && lane == 0) {  // the bytes before the row
 #pragma unroll
                     for (int w = 0; w < 4; w++) {
-                        const int n = int(mis) - 4 * w;
-                        v[i][w] &= n >= 4 ? 0u : n <= 0 ? ~0u : ~((1u << (8 * n)) - 1u);
+                        v[i][w] &= ~bytes_mask(int(mis) - 4 * w);
                     }
                 }
                 gs ^= crc32_nib_chunk(gt + 2048 * i, v[i]);
@@ -276,7 +274,7 @@ __global__ __launch_bounds__(kWG) void rs_crc32_rows_pipe_kernel(const uint32_t*
     }
 }
 
-// The rows pass with the fold on the matrix cores: rs_crc16_rows_mfma_kernel (rs_kernels.hip)
+// The rows pass with the fold on the matrix cores: rs_crc16_rows_mfma_kernel (rs_crc16_kernels.hip)
 // with a 32-bit register.  B = the tile's data, one data bit per fp4 nibble (forms x & 0x11..,
 // 0x22.., 0x44.., (x >> 1) & 0x44..), column m = lane & 15, k block j = lane >> 4; two MFMAs per
 // form, A = the weights of CRC bits 0-15 and 16-31 of tile t of an 8-tile group (MW, 64 KiB of
@@ -351,15 +349,13 @@ __global__ __launch_bounds__(kCrc32MfmaWG) void rs_crc32_rows_mfma_kernel(
                         const int64_t valid = int64_t(Sm) - int64_t((uint64_t(t0 + i) * kWave + lane) * 16);
 #pragma unroll
                         for (int w = 0; w < 4; w++) {
-                            const int64_t n = valid - 4 * w;
-                            d[w] &= n >= 4 ? ~0u : n <= 0 ? 0u : (1u << (8 * n)) - 1u;
+                            d[w] &= bytes_mask(valid - 4 * w);
                         }
                     }
                     if (UA && t0 + i == 0 && mis != 0u && lane == 0) {  // the bytes before the row
 #pragma unroll
                         for (int w = 0; w < 4; w++) {
-                            const int n = int(mis) - 4 * w;
-                            d[w] &= n >= 4 ? 0u : n <= 0 ? ~0u : ~((1u << (8 * n)) - 1u);
+                            d[w] &= ~bytes_mask(int(mis) - 4 * w);
                         }
                     }
 #pragma unroll

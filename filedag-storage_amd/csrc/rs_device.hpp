@@ -1,5 +1,4 @@
-// rs_device.hpp -- device helpers shared by the coding kernels (rs_kernels.hip,
-// rs_lds_kernels.hip).
+// rs_device.hpp -- device helpers shared by every kernel unit (coding, verify, CRC-16, CRC-32).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -35,6 +34,13 @@ __device__ __forceinline__ void st16u(uint8_t* p, u32x4 v) {
     else *reinterpret_cast<u32x4u*>(p) = v;
 }
 
+// A dword's mask of its first nb bytes (nb of any sign and size: the bytes of a chunk that lie
+// before the row's end S)
+template <class I>
+__device__ __forceinline__ uint32_t bytes_mask(I nb) {
+    return nb >= 4 ? ~0u : nb <= 0 ? 0u : (1u << (8 * nb)) - 1u;
+}
+
 // 16 bytes of a row at byte offset off; bytes at or past S read as zero (CRC passes: zero
 // bytes past the end only move the reference point, which the caller's shift accounts for)
 template <bool ALIGNED>
@@ -47,9 +53,7 @@ __device__ __forceinline__ u32x4 crc_chunk_load(const uint8_t* row, uint64_t off
             const int valid = int(S - off);
 #pragma unroll
             for (int w = 0; w < 4; w++) {
-                const int nb = valid - 4 * w;
-                const uint32_t mask = nb >= 4 ? ~0u : nb <= 0 ? 0u : (1u << (8 * nb)) - 1u;
-                v[w] &= mask;
+                v[w] &= bytes_mask(valid - 4 * w);
             }
         }
     } else if (off + 16 <= S) {

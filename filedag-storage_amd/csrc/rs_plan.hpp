@@ -7,10 +7,7 @@ namespace rsmi {
 
 constexpr int kWave = 64;       // CDNA wavefront
 constexpr int kWG = 256;        // threads per workgroup (4 waves)
-#ifndef RSMI_FAST_WG  // threads per workgroup of the coding kernel rs_fast_kernel (A/B builds)
-#define RSMI_FAST_WG 256
-#endif
-constexpr int kFastWG = RSMI_FAST_WG;
+constexpr int kFastWG = kWG;    // ... of the coding and verify kernels (one tile per wave)
 constexpr int kMaxK = 256;      // k + m <= 256 (erasure.go:22)
 constexpr int kMaxMT = 4;       // outputs per launch tile
 constexpr int kColDwords = 20;  // per input column: 5 table fields x 4 outputs
@@ -187,27 +184,17 @@ constexpr int kCrcMWOff = kCrcP4Off + kCrcP4Words;
 constexpr int kCrcFWWords = 4 * 4 * 64 * 4;       // fp4 weights of the fused encode + CRC kernel
 constexpr int kCrcFWOff = kCrcMWOff + kCrcMWWords;
 constexpr int kCrcTableWords = kCrcFWOff + kCrcFWWords;
-#ifndef RSMI_FUSED_UNIT
-#define RSMI_FUSED_UNIT 4
-#endif
-#ifndef RSMI_FUSED_COOP  // 1: a workgroup codes a unit (one tile per wave); 0: one wave codes a unit
-#define RSMI_FUSED_COOP 1
-#endif
 // launches of at most this many units combine their records in the fused kernel (one launch
 // instead of two; larger ones keep the separate combine, see rs_fused_mfma_kernel INL)
 #ifndef RSMI_FUSED_INLINE_UNITS
 #define RSMI_FUSED_INLINE_UNITS 64
 #endif
 constexpr uint32_t kFusedInlineUnits = RSMI_FUSED_INLINE_UNITS;
-// 1: such launches store the output rows after the unit's record is published (0: before it)
-#ifndef RSMI_FUSED_INL_DEFER
-#define RSMI_FUSED_INL_DEFER 1
-#endif
-// fused encode + CRC on the matrix cores: tiles per wave (one unit), 1, 2 or 4 (the two-shard
-// accumulators stay exact up to 4 tiles)
-constexpr int kFusedUnitTiles = RSMI_FUSED_UNIT;
-constexpr int kFusedUnitLog = kFusedUnitTiles == 4 ? 2 : kFusedUnitTiles == 2 ? 1 : 0;
-static_assert(kFusedUnitTiles == 1 << kFusedUnitLog, "unit of 1, 2 or 4 tiles");
+// fused encode + CRC on the matrix cores: a unit is 4 tiles, one per wave of its workgroup (the
+// two-shard accumulators stay exact up to 4 tiles)
+constexpr int kFusedUnitTiles = kWG / kWave;
+constexpr int kFusedUnitLog = 2;
+static_assert(kFusedUnitTiles == 1 << kFusedUnitLog, "a unit of 4 tiles");
 #ifndef RSMI_FUSED_WPS
 #define RSMI_FUSED_WPS 3
 #endif

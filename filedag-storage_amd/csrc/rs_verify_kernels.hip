@@ -1,7 +1,7 @@
 // rs_verify_kernels.hip -- Encoder.Verify on the GPU: is every stored parity row what the encode
 // of the block's data rows would produce?
 //
-// rs_verify_kernel runs rs_fast_kernel's GF(2^8) pipeline (rs_kernels.hip: v_perm tables in LDS,
+// rs_verify_kernel runs the coding kernels' GF(2^8) pipeline (rs_gf_tile.hpp: v_perm tables in LDS,
 // a ring of rows in flight, one scheduling region per column) over the tiles of the context's
 // encode plan, but where the encode stores its MT output chunks the verify loads the MT *stored*
 // parity chunks and compares.  It reads k + m rows and writes nothing: the same HBM bytes as the
@@ -19,16 +19,10 @@
 #include <cstdint>
 
 #include "rs_device.hpp"
+#include "rs_gf_tile.hpp"
 #include "rs_plan.hpp"
 
 namespace rsmi {
-
-// rows in flight per lane, as the coding kernels keep them (rs_kernels.hip rows_in_flight)
-template <int K, int MT>
-constexpr int verify_rows_in_flight() {
-    constexpr int cap = MT <= 2 ? 16 : 6;
-    return K < cap ? K : cap;
-}
 
 // K data rows in, MT (<= 4) stored parity rows compared, one 16-byte chunk per lane per row.
 // plan: a tile of the encode plan (in_row = 0..K-1, out_row = the tile's parity rows relative to
@@ -59,12 +53,12 @@ __global__ __launch_bounds__(kFastWG, kMinWavesPerSimd) void rs_verify_kernel(
     const uint32_t nw = gridDim.x * kWavesPerWG;
     // UA: each XCD takes one contiguous eighth of the tiles, as in rs_fast_kernel (a tile at an
     // odd address shares its first and last lines with its neighbours)
-    uint32_t wg = blockIdx.x;
-    if (UA && (gridDim.x & 7u) == 0u) wg = (wg & 7u) * (gridDim.x >> 3) + (wg >> 3);
+    const uint32_t wg =
+        UA ? tile_group(blockIdx.x, gridDim.x, (gridDim.x & 7u) ? 0u : gridDim.x) : uint32_t(blockIdx.x);
     uint32_t t = wg * kWavesPerWG + wid;
     if (t >= ntiles) return;
 
-    constexpr int P = verify_rows_in_flight<K, MT>();
+    constexpr int P = rows_in_flight<K, MT>();
     constexpr int PR = MT < P ? MT : P;  // parity rows that go through the ring
     uint64_t in_off[K], par_off[MT];
     uint32_t flag[MT];
@@ -76,26 +70,19 @@ __global__ __launch_bounds__(kFastWG, kMinWavesPerSimd) void rs_verify_kernel(
         par_off[j] = uint64_t(flag[j]) * par_rs;
     }
 
-    uint32_t blk = t / tpb;
-    uint32_t tib = t - blk * tpb;
-    const uint32_t step_b = nw / tpb, step_t = nw - step_b * tpb;
-
-    for (; t < ntiles; t += nw) {
+    for (TileWalk tw(t, nw, tpb); t < ntiles; t += nw, tw.next(tpb)) {
+        const uint32_t blk = tw.blk;
         const uint8_t* ib = in + uint64_t(blk) * in_bs;
         const uint8_t* pb = par + uint64_t(blk) * par_bs;
-        const uint32_t ch = tib * kWave + lane;
-        const uint32_t chl = ch < cpb ? ch : cpb - 1;  // load chunk, clamped: loads stay unconditional
-        const uint32_t win = UA ? (chl * 16u < S - 16u ? chl * 16u : S - 16u) : 0u;
+        const LaneChunk lc = lane_chunk<UA>(tw.tib, lane, cpb, S);
+        const uint32_t ch = lc.ch, chl = lc.chl, win = lc.win;
         // the bytes of the lane's chunk that count: none for a lane past the row's last chunk; UA:
         // every byte of a window (it lies in [0, S)); aligned: the bytes before S
         uint32_t mk[4];
         {
             const int valid = ch < cpb ? (UA ? 16 : int(S) - int(ch * 16u)) : 0;
 #pragma unroll
-            for (int w = 0; w < 4; w++) {
-                const int nb = valid - 4 * w;
-                mk[w] = nb >= 4 ? ~0u : nb <= 0 ? 0u : (1u << (8 * nb)) - 1u;
-            }
+            for (int w = 0; w < 4; w++) mk[w] = bytes_mask(valid - 4 * w);
         }
         auto load_col = [&](int c) {
             if constexpr (UA)
@@ -117,67 +104,15 @@ __global__ __launch_bounds__(kFastWG, kMinWavesPerSimd) void rs_verify_kernel(
 #pragma unroll
         for (int j = PR; j < MT; j++) xs[j - PR] = load_par(j);
 
-        uint32_t acc[MT][4], pend[MT][4];
-        // opaque per-tile table base: keeps the K*20 table words out of registers across tiles
-        uint32_t tb = 0;
-        asm volatile("" : "+v"(tb));
-        const u32x4* tbl = s_tbl + tb;
-        u32x4 Tn[5];
-#pragma unroll
-        for (int f = 0; f < 5; f++) Tn[f] = tbl[f];
-
-#pragma unroll
-        for (int c = 0; c < K; c++) {
-            const int slot = c % P;
-            u32x4 T[5];
-#pragma unroll
-            for (int f = 0; f < 5; f++) T[f] = Tn[f];
-#pragma unroll
-            for (int w = 0; w < 4; w++) {
-                const uint32_t x = u4get(v[slot], w);
-                const uint32_t s1 = x & 0x07070707u;
-                const uint32_t s2 = (x >> 3) & 0x07070707u;
-                const uint32_t s3 = (x >> 6) & 0x03030303u;
-#pragma unroll
-                for (int j = 0; j < MT; j++) {
-                    const uint32_t p1 = __builtin_amdgcn_perm(u4get(T[1], j), u4get(T[0], j), s1);
-                    const uint32_t p2 = __builtin_amdgcn_perm(u4get(T[3], j), u4get(T[2], j), s2);
-                    const uint32_t p3 = __builtin_amdgcn_perm(u4get(T[4], j), u4get(T[4], j), s3);
-                    uint32_t& a = acc[j][w];
-                    uint32_t& q = pend[j][w];
-                    if (c == 0 && K == 1) {
-                        a = xor3(p1, p2, p3);
-                    } else if (c == 0) {
-                        a = p1 ^ p2;
-                        q = p3;
-                    } else if (c & 1) {
-                        a = xor3(a, p1, p2);
-                        a = xor3(a, p3, q);
-                    } else if (c == K - 1) {
-                        a = xor3(a, p1, p2);
-                        a ^= p3;
-                    } else {
-                        a = xor3(a, p1, p2);
-                        q = p3;
-                    }
-                }
-            }
-            // the freed slot takes the next input row, or, once those are all issued, a stored
-            // parity row: parity row j rides in slot (K - P + j) % P
+        uint32_t acc[MT][4];
+        // the freed slot takes the next input row, or, once those are all issued, a stored
+        // parity row: parity row j rides in slot (K - P + j) % P
+        gf_tile_columns<K, MT, P>(s_tbl, v, acc, GfNone{}, GfNone{}, GfNone{}, [&](int c, u32x4& x) {
             if (c + P < K)
-                v[slot] = load_col(c + P);
+                x = load_col(c + P);
             else if (c + P - K < PR)
-                v[slot] = load_par(c + P - K);
-            if (c + 1 < K) {
-#pragma unroll
-                for (int f = 0; f < 5; f++) Tn[f] = tbl[(c + 1) * 5 + f];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int j = 0; j < MT; j++)
-#pragma unroll
-            for (int w = 0; w < 4; w++) asm volatile("" : "+v"(acc[j][w]));
+                x = load_par(c + P - K);
+        });
 
 #pragma unroll
         for (int j = 0; j < MT; j++) {
@@ -189,13 +124,6 @@ __global__ __launch_bounds__(kFastWG, kMinWavesPerSimd) void rs_verify_kernel(
             // difference: a vector atomic (no return value), never issued on a clean tile
             if (__builtin_amdgcn_ballot_w64(d != 0u) != 0ull && lane == 0u)
                 __hip_atomic_fetch_or(bad + uint64_t(blk) * m + flag[j], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-
-        blk += step_b;
-        tib += step_t;
-        if (tib >= tpb) {
-            tib -= tpb;
-            blk++;
         }
     }
 }

@@ -197,7 +197,7 @@ int launch_plan_crc(rsmi_ctx* c, const Plan& plan, const uint8_t* in, size_t in_
         // launch instead of two; big ones keep the separate combine (rs_fused_mfma_kernel INL)
         void* inl_fn = aligned ? (tb ? kt.fused_inl_tb : kt.fused_inl)[tile.K][tile.MT]
                                : (tb ? kt.fused_ua_inl_tb : kt.fused_ua_inl)[tile.K][tile.MT];
-        const bool inline_combine = RSMI_FUSED_COOP && inl_fn && nblocks * upb <= kFusedInlineUnits;
+        const bool inline_combine = inl_fn && nblocks * upb <= kFusedInlineUnits;
         if (inline_combine) fn = inl_fn;
         if (!fn) return RSMI_ERR_INVALID_ARG;  // a table shape without the two-launch form, too big to combine inside
         // per-block unit counters of the inline combine: zeroed once when allocated, and every
@@ -235,8 +235,7 @@ int launch_plan_crc(rsmi_ctx* c, const Plan& plan, const uint8_t* in, size_t in_
             void* bases = tb ? static_cast<void*>(&tbl_args) : static_cast<void*>(&nob);
             void* args[] = {&pd,    &inb,   &outb,   &ibs, &irs, &obs, &ors, &S32, &cpb32,
                             &tpb32, &upb32, &nunits, &ctb, &rb,  &cb,  &rw,  &sh,  bases};
-            const uint32_t wgs = RSMI_FUSED_COOP ? nunits : (nunits + kWG / kWave - 1) / (kWG / kWave);
-            HIP_TRY(hipLaunchKernel(fn, dim3(wgs), dim3(kWG), args, 0, st));
+            HIP_TRY(hipLaunchKernel(fn, dim3(nunits), dim3(kWG), args, 0, st));  // a workgroup per unit
         }
         if (!inline_combine) {
             uint32_t nacc32 = uint32_t(nacc), nsh32 = uint32_t(nsh);

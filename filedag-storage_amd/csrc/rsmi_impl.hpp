@@ -5,7 +5,8 @@
 //   rsmi_coalesce.cpp  group commit of concurrent single-block calls
 //   rsmi_verify.cpp    Encoder.Verify: stored parity checked against the data rows
 // No CPU compute path anywhere: every byte of parity, reconstructed data or CRC and every verify
-// flag comes out of the HIP kernels (rs_kernels.hip, rs_crc32_kernels.hip, rs_verify_kernels.hip).
+// flag comes out of the HIP kernels (rs_kernels.hip, rs_kernels_tb.hip, rs_crc16_kernels.hip, rs_crc32_kernels.hip,
+// rs_verify_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -67,7 +68,7 @@ struct Staging {
 
 // Launch every tile of a plan over nblocks blocks.
 // Fused CRC-16 output of an encode launch (rs_fast_kernel CRC variants): per-tile quad records
-// of every shard and, for unaligned-window layouts, the rows' last chunks (rs_kernels.hip).
+// of every shard and, for unaligned-window layouts, the rows' last chunks (rs_coding_kernels.hpp).
 struct CrcFuse {
     const uint32_t* tbl = nullptr;
     uint32_t* rec = nullptr;

@@ -1,4 +1,4 @@
-"""The completion-flag release covers every wave's stores (launch_done, rs_kernels.hip).
+"""The completion-flag release covers every wave's stores (launch_done, rs_coding_kernels.hpp).
 
 Compiles the table-of-bases kernels to gfx950 assembly and runs tools/check_flag_fence.py: every
 workgroup barrier that precedes the system-scope flag atomic must be reached with no vector store

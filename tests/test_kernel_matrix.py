@@ -7,7 +7,8 @@ own unrolled code, which no other shape executes: this module runs every one of 
 the launch label (rsmi_last_kernel) that the instantiation was reached, and compares parity,
 rebuilt rows and R(row) with oracle_lib.  Shapes without an instantiation must fall to
 rs_generic_kernel (and, with CRC, to the separate pass), whose two grid-stride loops run a second
-iteration here.  Leg 0 keeps the tables below equal to the dispatch table in rs_kernels.hip.
+iteration here.  Leg 0 keeps the tables below equal to the dispatch table in rs_kernels.hip and
+rs_kernels_tb.hip.
 
 Everything is bit-exact: there are no tolerances.
 """
@@ -23,7 +24,9 @@ import pytest
 import oracle_lib as orc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS_HIP = os.path.join(ROOT, "filedag-storage_amd", "csrc", "rs_kernels.hip")
+CSRC = os.path.join(ROOT, "filedag-storage_amd", "csrc")
+KERNELS_HIP = os.path.join(CSRC, "rs_kernels.hip")        # fill_k, fill_km, fill_inl
+KERNELS_TB_HIP = os.path.join(CSRC, "rs_kernels_tb.hip")  # fill_tb_k, fill_tb_km, fill_tb_fused, fill_tb_fused_inl
 
 # ---------------------------------------------------------------- the dispatch table, restated
 KS = [1, 2, 3, 4, 5, 6, 8, 10, 12, 16]                      # fill_k<K>: six forms for MT = 1..4
@@ -95,18 +98,22 @@ def _calls(src, name, nargs):
 
 def test_tables_match_source():
     """The module's tables equal the arguments of fill_k / fill_inl / fill_tb_k / fill_tb_fused /
-    fill_tb_fused_inl in rs_kernels.hip: an instantiation added without extending this sweep fails
-    the CPU suite."""
+    fill_tb_fused_inl in rs_kernels.hip (the table-less forms) and rs_kernels_tb.hip (the
+    table-of-bases forms): an instantiation added without extending this sweep fails the CPU suite."""
     with open(KERNELS_HIP) as f:
         src = f.read()
+    with open(KERNELS_TB_HIP) as f:
+        src_tb = f.read()
     assert _calls(src, "fill_k", 1) == KS
     assert _calls(src, "fill_inl", 2) == INL_SHAPES
-    assert _calls(src, "fill_tb_k", 1) == TB_KS
-    assert _calls(src, "fill_tb_fused", 2) == TB_FUSED_SHAPES
-    assert _calls(src, "fill_tb_fused_inl", 2) == TB_FUSED_INL_SHAPES
+    assert _calls(src_tb, "fill_tb_k", 1) == TB_KS
+    assert _calls(src_tb, "fill_tb_fused", 2) == TB_FUSED_SHAPES
+    assert _calls(src_tb, "fill_tb_fused_inl", 2) == TB_FUSED_INL_SHAPES
+    # the table-of-bases forms are filled in their own unit only
+    assert not re.search(r"\bfill_tb_\w+<", src)
     # fill_k and fill_tb_k expand to MT = 1..4 (the templates' K stays symbolic in the source)
     assert re.findall(r"\bfill_km<K,\s*(\d+)>\(", src) == [str(m) for m in MTS]
-    assert re.findall(r"\bfill_tb_km<K,\s*(\d+)>\(", src) == [str(m) for m in MTS]
+    assert re.findall(r"\bfill_tb_km<K,\s*(\d+)>\(", src_tb) == [str(m) for m in MTS]
     assert not set(k for k, _ in GENERIC_SHAPES) & set(KS)
     assert sorted(set(KS) | set(k for k, _ in GENERIC_SHAPES)) == list(range(1, 17))
     assert set(TB_KS) <= set(KS) and all(k in TB_KS for k, _ in TB_FUSED_SHAPES + TB_FUSED_INL_SHAPES)

@@ -2,7 +2,7 @@
 """Check the completion-flag release in the gfx950 assembly of the table-of-bases kernels.
 
 Every kernel that counts its workgroups with a system-scope global_atomic_add (launch_done,
-csrc/rs_kernels.hip) must have, in every wave, no vector store still outstanding when the
+csrc/rs_coding_kernels.hpp) must have, in every wave, no vector store still outstanding when the
 workgroup barrier before that atomic passes: on every straight-line path from a vector store to
 the flag's s_barrier (the barrier whose next barrier-or-atomic in the text is the flag atomic)
 there has to be an `s_waitcnt vmcnt(0)`.  The check is on program text: a store followed by a

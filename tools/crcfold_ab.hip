@@ -1,7 +1,7 @@
 // crcfold_ab.hip -- diagnostic A/B (not part of the product): two ways to fold a 16-byte chunk
 // into its datanode CRC-16 value R(chunk) (howeyc IBM, reflected 0xA001, crc16.hpp).
 //
-//   nib   -- the product's fold (rs_kernels.hip crc_nib_chunk): 32 positional nibble lookups per
+//   nib   -- the product's fold (rs_crc16_kernels.hip crc_nib_chunk): 32 positional nibble lookups per
 //            chunk in 16-entry u16 LDS tables (conflict-free), one byte extract per lookup.
 //   vperm -- byte-transposed v_perm fold (VERDICT r1 item 3's candidate): a lane holds the same
 //            chunk of 4 rows, transposes them so one dword carries byte p of all 4 rows, and runs

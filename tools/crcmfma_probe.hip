@@ -4,7 +4,7 @@
 // GF(2) matrix product.  An MFMA sums integer products; with every product of a set bit and a
 // set weight equal to one unit, bit 0 of the count (fp4) or bit 7 of the i8 sum is the parity.
 //
-//   nib  -- the fused encode's fold (rs_kernels.hip crc_row): quad-relative nibble tables Q in
+//   nib  -- the fused encode's fold (rs_coding_kernels.hpp crc_row): quad-relative nibble tables Q in
 //           LDS, 32 lookups per 16-byte chunk, two DPP XORs per quad; 16 u16 records per tile.
 //   fp4  -- v_mfma_scale_f32_16x16x128_f8f6f4, fp4 (e2m1) operands: the data operand takes one
 //           bit per nibble (v & 0x11111111, 0x22.., 0x44.., (v >> 1) & 0x44..: 5 VALU per dword
