@@ -165,6 +165,17 @@ struct VerifyKernelTable {
 const VerifyKernelTable& verify_kernels();
 void* compare_rows_kernel();
 
+// rsmi_locate (rs_locate_kernels.hip): rs_locate_kernel per (K, MT = m), m = 2..4, aligned and
+// unaligned-window layouts (null when the shape has none), the verdict kernel that follows every
+// locate launch, and the byte-granular kernel of the fallback
+struct LocateKernelTable {
+    void* fn[17][kMaxMT + 1];
+    void* ua[17][kMaxMT + 1];
+};
+const LocateKernelTable& locate_kernels();
+void* locate_verdict_kernel();
+void* locate_rows_kernel();
+
 // CRC-16 of shard rows (crc16.hpp): the device table buffer holds P[15][2][256] (the powers
 // A^(2^i), byte-sliced) and N[32][16] (u16); a wave folds kCrcSegTiles 1 KiB tiles of one row
 // with one N lookup per nibble (16-entry tables: each wave-wide lookup touches 8 distinct

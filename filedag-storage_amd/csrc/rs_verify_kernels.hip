@@ -21,111 +21,20 @@
 #include "rs_device.hpp"
 #include "rs_gf_tile.hpp"
 #include "rs_plan.hpp"
+#include "rs_verify_tile.hpp"
 
 namespace rsmi {
 
-// K data rows in, MT (<= 4) stored parity rows compared, one 16-byte chunk per lane per row.
-// plan: a tile of the encode plan (in_row = 0..K-1, out_row = the tile's parity rows relative to
-// the parity base).  bad: the launch's first block's flags, m words per block.
-// UA: rows at any byte alignment and pitch (S >= 16), a lane's window at min(16 ch, S - 16).
-// The stored parity chunks are members of the row ring: parity row j takes the slot that input
-// row K - P + j leaves (its load is issued P columns before the GF work ends), and with fewer
-// slots than parity rows (K < MT) the rest are loaded ahead of the column loop, so no load waits
-// behind the GF work.  Every load is nontemporal: nothing is read twice.
-// Launch geometry: one tile per wave; the loop strides over further tiles only when the caller
-// caps the grid (option waves_per_cu).
+// The tile loop is verify_tiles (rs_verify_tile.hpp), shared with rs_locate_kernel.
 template <int K, int MT, bool UA>
 __global__ __launch_bounds__(kFastWG, kMinWavesPerSimd) void rs_verify_kernel(
     const RsPlanDev* __restrict__ plan, const uint8_t* __restrict__ in, const uint8_t* __restrict__ par,
     uint64_t in_bs, uint64_t in_rs, uint64_t par_bs, uint64_t par_rs, uint32_t S, uint32_t cpb, uint32_t tpb,
     uint32_t ntiles, uint32_t* __restrict__ bad, uint32_t m) {
     __shared__ u32x4 s_tbl[K * kColDwords / 4];
-    {
-        const uint32_t* src = plan->tbl;
-        uint32_t* dst = reinterpret_cast<uint32_t*>(s_tbl);
-        for (int i = threadIdx.x; i < K * kColDwords; i += kFastWG) dst[i] = src[i];
-    }
-    __syncthreads();
-
-    constexpr uint32_t kWavesPerWG = kFastWG / kWave;
-    const uint32_t lane = threadIdx.x & (kWave - 1);
-    const uint32_t wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-    const uint32_t nw = gridDim.x * kWavesPerWG;
-    // UA: each XCD takes one contiguous eighth of the tiles, as in rs_fast_kernel (a tile at an
-    // odd address shares its first and last lines with its neighbours)
-    const uint32_t wg =
-        UA ? tile_group(blockIdx.x, gridDim.x, (gridDim.x & 7u) ? 0u : gridDim.x) : uint32_t(blockIdx.x);
-    uint32_t t = wg * kWavesPerWG + wid;
-    if (t >= ntiles) return;
-
-    constexpr int P = rows_in_flight<K, MT>();
-    constexpr int PR = MT < P ? MT : P;  // parity rows that go through the ring
-    uint64_t in_off[K], par_off[MT];
-    uint32_t flag[MT];
-#pragma unroll
-    for (int c = 0; c < K; c++) in_off[c] = uint64_t(plan->in_row[c]) * in_rs;
-#pragma unroll
-    for (int j = 0; j < MT; j++) {
-        flag[j] = plan->out_row[j];
-        par_off[j] = uint64_t(flag[j]) * par_rs;
-    }
-
-    for (TileWalk tw(t, nw, tpb); t < ntiles; t += nw, tw.next(tpb)) {
-        const uint32_t blk = tw.blk;
-        const uint8_t* ib = in + uint64_t(blk) * in_bs;
-        const uint8_t* pb = par + uint64_t(blk) * par_bs;
-        const LaneChunk lc = lane_chunk<UA>(tw.tib, lane, cpb, S);
-        const uint32_t ch = lc.ch, chl = lc.chl, win = lc.win;
-        // the bytes of the lane's chunk that count: none for a lane past the row's last chunk; UA:
-        // every byte of a window (it lies in [0, S)); aligned: the bytes before S
-        uint32_t mk[4];
-        {
-            const int valid = ch < cpb ? (UA ? 16 : int(S) - int(ch * 16u)) : 0;
-#pragma unroll
-            for (int w = 0; w < 4; w++) mk[w] = bytes_mask(valid - 4 * w);
-        }
-        auto load_col = [&](int c) {
-            if constexpr (UA)
-                return ld16u<true>(ib + in_off[c] + win);
-            else
-                return ld16<true>(reinterpret_cast<const u32x4*>(ib + in_off[c]) + chl);
-        };
-        auto load_par = [&](int j) {
-            if constexpr (UA)
-                return ld16u<true>(pb + par_off[j] + win);
-            else
-                return ld16<true>(reinterpret_cast<const u32x4*>(pb + par_off[j]) + chl);
-        };
-
-        u32x4 v[P];
-        u32x4 xs[MT > PR ? MT - PR : 1];  // K < MT: the parity rows the ring has no slot for
-#pragma unroll
-        for (int c = 0; c < P; c++) v[c] = load_col(c);
-#pragma unroll
-        for (int j = PR; j < MT; j++) xs[j - PR] = load_par(j);
-
-        uint32_t acc[MT][4];
-        // the freed slot takes the next input row, or, once those are all issued, a stored
-        // parity row: parity row j rides in slot (K - P + j) % P
-        gf_tile_columns<K, MT, P>(s_tbl, v, acc, GfNone{}, GfNone{}, GfNone{}, [&](int c, u32x4& x) {
-            if (c + P < K)
-                x = load_col(c + P);
-            else if (c + P - K < PR)
-                x = load_par(c + P - K);
-        });
-
-#pragma unroll
-        for (int j = 0; j < MT; j++) {
-            const u32x4 sp = j < PR ? v[(K - P + j) % P] : xs[j < PR ? 0 : j - PR];
-            uint32_t d = 0;
-#pragma unroll
-            for (int w = 0; w < 4; w++) d |= (acc[j][w] ^ u4get(sp, w)) & mk[w];
-            // one relaxed agent-scope OR from one lane, and only when some lane of the wave saw a
-            // difference: a vector atomic (no return value), never issued on a clean tile
-            if (__builtin_amdgcn_ballot_w64(d != 0u) != 0ull && lane == 0u)
-                __hip_atomic_fetch_or(bad + uint64_t(blk) * m + flag[j], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    stage_tables<K>(s_tbl, plan, nullptr);
+    verify_tiles<K, MT, UA, false>(s_tbl, plan, in, par, in_bs, in_rs, par_bs, par_rs, S, cpb, tpb, ntiles, bad, m,
+                                   nullptr);
 }
 
 // Fallback compare for shapes rs_verify_kernel is not built for: rows a (the encode of the data

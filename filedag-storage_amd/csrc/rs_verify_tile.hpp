@@ -1,0 +1,191 @@
+// rs_verify_tile.hpp -- the tile loop of rs_verify_kernel (rs_verify_kernels.hip) and of
+// rs_locate_kernel (rs_locate_kernels.hip): the coding kernels' GF(2^8) pipeline over the tiles of
+// the encode plan, the stored parity chunks loaded where the encode would store, the syndromes
+//   syn_j = encode(data)_j ^ stored parity_j
+// formed in registers and bad[block * m + parity row] raised where one is non-zero.  LOC: on a
+// tile with a non-zero syndrome the wave goes on to name the shards that explain it (locate_tile).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "rs_device.hpp"
+#include "rs_gf_tile.hpp"
+#include "rs_plan.hpp"
+
+namespace rsmi {
+
+// The shards that explain a dirty tile, ANDed into the block's candidate word *cand (bit x: shard
+// x; the caller set the word to all-ones before the launch).  syn: the lane's masked syndromes;
+// rtbl: the v_perm tables of the ratio matrix R[j][c] = M[j][c] / M[0][c] (rsmi_locate_matrix)
+// in LDS, laid out as a plan's tables.  Over the bytes where some syn_j != 0,
+//   data shard c explains    iff  syn_j == R[j][c] * syn_0 for every j >= 1,
+//   parity shard j explains  iff  syn_i == 0 for every i != j;
+// a byte whose syndromes are all zero passes every test (R * 0 = 0), so the tests run over all 16
+// bytes of every lane unconditionally and a clean lane (or one past the row's end) votes for every
+// shard.  Each test is one ballot over the wave, so the wave's AND is built in scalar registers;
+// one lane then issues one relaxed agent-scope atomic AND with no return value.  Rows that
+// overlap (UA windows) are tested twice, which an AND does not see.
+template <int K, int MT>
+__device__ __forceinline__ void locate_tile(const u32x4* rtbl, const uint32_t (&syn)[MT][4], uint32_t lane,
+                                            uint32_t* cand) {
+    uint32_t wm = 0;
+#pragma unroll
+    for (int j = 0; j < MT; j++) {
+        uint32_t o = 0;
+#pragma unroll
+        for (int i = 0; i < MT; i++)
+            if (i != j) o |= syn[i][0] | syn[i][1] | syn[i][2] | syn[i][3];
+        if (__builtin_amdgcn_ballot_w64(o != 0u) == 0ull) wm |= 1u << (K + j);
+    }
+    // the selector words of syn_0, shared by every column (rs_gf_tile.hpp)
+    uint32_t s1[4], s2[4], s3[4];
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        s1[w] = syn[0][w] & 0x07070707u;
+        s2[w] = (syn[0][w] >> 3) & 0x07070707u;
+        s3[w] = (syn[0][w] >> 6) & 0x03030303u;
+    }
+    // rolled: a dirty tile is the rare case, the code stays small
+#pragma unroll 1
+    for (int c = 0; c < K; c++) {
+        u32x4 T[5];
+#pragma unroll
+        for (int f = 0; f < 5; f++) T[f] = rtbl[c * 5 + f];
+        uint32_t diff = 0;
+#pragma unroll
+        for (int j = 1; j < MT; j++)
+#pragma unroll
+            for (int w = 0; w < 4; w++) {
+                const uint32_t p1 = __builtin_amdgcn_perm(u4get(T[1], j), u4get(T[0], j), s1[w]);
+                const uint32_t p2 = __builtin_amdgcn_perm(u4get(T[3], j), u4get(T[2], j), s2[w]);
+                const uint32_t p3 = __builtin_amdgcn_perm(u4get(T[4], j), u4get(T[4], j), s3[w]);
+                diff |= xor3(p1, p2, p3) ^ syn[j][w];
+            }
+        if (__builtin_amdgcn_ballot_w64(diff != 0u) == 0ull) wm |= 1u << c;
+    }
+    if (lane == 0u) (void)__hip_atomic_fetch_and(cand, wm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// K data rows in, MT (<= 4) stored parity rows compared, one 16-byte chunk per lane per row.
+// plan: a tile of the encode plan (in_row = 0..K-1, out_row = the tile's parity rows relative to
+// the parity base).  bad: the launch's first block's flags, m words per block.  s_tbl: the plan's
+// tables in LDS (LOC: followed by the ratio tables), staged and the barrier passed by the caller.
+// UA: rows at any byte alignment and pitch (S >= 16), a lane's window at min(16 ch, S - 16).
+// The stored parity chunks are members of the row ring: parity row j takes the slot that input
+// row K - P + j leaves (its load is issued P columns before the GF work ends), and with fewer
+// slots than parity rows (K < MT) the rest are loaded ahead of the column loop, so no load waits
+// behind the GF work.  Every load is nontemporal: nothing is read twice.
+// Launch geometry: one tile per wave; the loop strides over further tiles only when the caller
+// caps the grid (option waves_per_cu).
+// LOC (the encode plan is this one tile, MT = m >= 2): cand, the launch's first block's candidate
+// word, one per block.
+template <int K, int MT, bool UA, bool LOC>
+__device__ __forceinline__ void verify_tiles(const u32x4* s_tbl, const RsPlanDev* __restrict__ plan,
+                                             const uint8_t* __restrict__ in, const uint8_t* __restrict__ par,
+                                             uint64_t in_bs, uint64_t in_rs, uint64_t par_bs, uint64_t par_rs,
+                                             uint32_t S, uint32_t cpb, uint32_t tpb, uint32_t ntiles,
+                                             uint32_t* __restrict__ bad, uint32_t m, uint32_t* __restrict__ cand) {
+    constexpr uint32_t kWavesPerWG = kFastWG / kWave;
+    const uint32_t lane = threadIdx.x & (kWave - 1);
+    const uint32_t wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+    const uint32_t nw = gridDim.x * kWavesPerWG;
+    // UA: each XCD takes one contiguous eighth of the tiles, as in rs_fast_kernel (a tile at an
+    // odd address shares its first and last lines with its neighbours)
+    const uint32_t wg =
+        UA ? tile_group(blockIdx.x, gridDim.x, (gridDim.x & 7u) ? 0u : gridDim.x) : uint32_t(blockIdx.x);
+    uint32_t t = wg * kWavesPerWG + wid;
+    if (t >= ntiles) return;
+
+    constexpr int P = rows_in_flight<K, MT>();
+    constexpr int PR = MT < P ? MT : P;  // parity rows that go through the ring
+    uint64_t in_off[K], par_off[MT];
+    uint32_t flag[MT];
+#pragma unroll
+    for (int c = 0; c < K; c++) in_off[c] = uint64_t(plan->in_row[c]) * in_rs;
+#pragma unroll
+    for (int j = 0; j < MT; j++) {
+        flag[j] = plan->out_row[j];
+        par_off[j] = uint64_t(flag[j]) * par_rs;
+    }
+
+    for (TileWalk tw(t, nw, tpb); t < ntiles; t += nw, tw.next(tpb)) {
+        const uint32_t blk = tw.blk;
+        const uint8_t* ib = in + uint64_t(blk) * in_bs;
+        const uint8_t* pb = par + uint64_t(blk) * par_bs;
+        const LaneChunk lc = lane_chunk<UA>(tw.tib, lane, cpb, S);
+        const uint32_t ch = lc.ch, chl = lc.chl, win = lc.win;
+        // the bytes of the lane's chunk that count: none for a lane past the row's last chunk; UA:
+        // every byte of a window (it lies in [0, S)); aligned: the bytes before S
+        uint32_t mk[4];
+        {
+            const int valid = ch < cpb ? (UA ? 16 : int(S) - int(ch * 16u)) : 0;
+#pragma unroll
+            for (int w = 0; w < 4; w++) mk[w] = bytes_mask(valid - 4 * w);
+        }
+        auto load_col = [&](int c) {
+            if constexpr (UA)
+                return ld16u<true>(ib + in_off[c] + win);
+            else
+                return ld16<true>(reinterpret_cast<const u32x4*>(ib + in_off[c]) + chl);
+        };
+        auto load_par = [&](int j) {
+            if constexpr (UA)
+                return ld16u<true>(pb + par_off[j] + win);
+            else
+                return ld16<true>(reinterpret_cast<const u32x4*>(pb + par_off[j]) + chl);
+        };
+
+        u32x4 v[P];
+        u32x4 xs[MT > PR ? MT - PR : 1];  // K < MT: the parity rows the ring has no slot for
+#pragma unroll
+        for (int c = 0; c < P; c++) v[c] = load_col(c);
+#pragma unroll
+        for (int j = PR; j < MT; j++) xs[j - PR] = load_par(j);
+
+        uint32_t acc[MT][4];
+        // the freed slot takes the next input row, or, once those are all issued, a stored
+        // parity row: parity row j rides in slot (K - P + j) % P
+        gf_tile_columns<K, MT, P>(s_tbl, v, acc, GfNone{}, GfNone{}, GfNone{}, [&](int c, u32x4& x) {
+            if (c + P < K)
+                x = load_col(c + P);
+            else if (c + P - K < PR)
+                x = load_par(c + P - K);
+        });
+
+        uint32_t syn[MT][4];
+        uint64_t dirty = 0;  // the lanes that saw a non-zero syndrome (wave-uniform)
+#pragma unroll
+        for (int j = 0; j < MT; j++) {
+            const u32x4 sp = j < PR ? v[(K - P + j) % P] : xs[j < PR ? 0 : j - PR];
+            uint32_t d = 0;
+#pragma unroll
+            for (int w = 0; w < 4; w++) {
+                syn[j][w] = (acc[j][w] ^ u4get(sp, w)) & mk[w];
+                d |= syn[j][w];
+            }
+            // one relaxed agent-scope OR from one lane, and only when some lane of the wave saw a
+            // difference: a vector atomic (no return value), never issued on a clean tile
+            const uint64_t dj = __builtin_amdgcn_ballot_w64(d != 0u);
+            if (dj != 0ull && lane == 0u)
+                __hip_atomic_fetch_or(bad + uint64_t(blk) * m + flag[j], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if constexpr (LOC) dirty |= dj;
+        }
+        if constexpr (LOC) {
+            // a clean tile does nothing more: no store, no atomic
+            if (dirty != 0ull) locate_tile<K, MT>(s_tbl + K * (kColDwords / 4), syn, lane, cand + blk);
+        }
+    }
+}
+
+// the plan's tables (and, when given, the ratio plan's behind them) into LDS, by the workgroup
+template <int K>
+__device__ __forceinline__ void stage_tables(u32x4* s_tbl, const RsPlanDev* plan, const RsPlanDev* rplan) {
+    uint32_t* dst = reinterpret_cast<uint32_t*>(s_tbl);
+    for (int i = threadIdx.x; i < K * kColDwords; i += kFastWG) dst[i] = plan->tbl[i];
+    if (rplan)
+        for (int i = threadIdx.x; i < K * kColDwords; i += kFastWG) dst[K * kColDwords + i] = rplan->tbl[i];
+    __syncthreads();
+}
+
+}  // namespace rsmi

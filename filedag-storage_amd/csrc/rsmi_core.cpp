@@ -456,6 +456,10 @@ void rsmi_close(rsmi_ctx* c) {
             if (!c->verify_scratch.empty()) (void)hipDeviceSynchronize();
             for (auto& e : c->verify_scratch)
                 if (e.second.p) (void)hipFree(e.second.p);
+            if (!c->locate_scratch.empty()) (void)hipDeviceSynchronize();
+            for (auto& e : c->locate_scratch)
+                if (e.second.p) (void)hipFree(e.second.p);
+            if (c->d_locate_tbl) (void)hipFree(c->d_locate_tbl);
             if (c->d_crc32_tbl) (void)hipFree(c->d_crc32_tbl);
             if (c->d_crc32) (void)hipFree(c->d_crc32);
         }

@@ -4,9 +4,10 @@
 //   rsmi_crc.cpp       datanode CRC-16 on the GPU (separate pass and fused into the encode)
 //   rsmi_coalesce.cpp  group commit of concurrent single-block calls
 //   rsmi_verify.cpp    Encoder.Verify: stored parity checked against the data rows
+//   rsmi_locate.cpp    rsmi_locate: the shard that breaks a stripe, from Verify's syndromes
 // No CPU compute path anywhere: every byte of parity, reconstructed data or CRC and every verify
 // flag comes out of the HIP kernels (rs_kernels.hip, rs_kernels_tb.hip, rs_crc16_kernels.hip, rs_crc32_kernels.hip,
-// rs_verify_kernels.hip).
+// rs_verify_kernels.hip, rs_locate_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -143,6 +144,10 @@ struct rsmi_ctx {
         size_t cap = 0;
     };
     std::map<hipStream_t, VerifyScratch> verify_scratch;
+    // rsmi_locate (rsmi_locate.cpp): per stream the candidate words (and the flags, when the
+    // caller takes none) of its launches; the fallback kernel's tables, uploaded on first use
+    std::map<hipStream_t, VerifyScratch> locate_scratch;
+    uint8_t* d_locate_tbl = nullptr;
     rsmi::Crc32Shift crc32_shift{};  // launch_crc32's per-S shift matrix, for crc32_shift_S
     uint64_t crc32_shift_S = ~uint64_t(0);
     CrcScratch own_scratch;  // the fused encode + CRC-16's scratch on the context's own streams
@@ -265,9 +270,43 @@ int reconstruct_host_impl(rsmi_ctx* c, uint8_t* shards, size_t block_stride, siz
 // Encoder.Verify of nblocks blocks (rsmi_verify.cpp; caller holds ctx->mu): bad[b*m + j], device
 // memory, zeroed here on the stream, then non-zero where stored parity row j of block b differs
 // from the encode of the block's data rows.  Stream-ordered, no synchronisation.
+// loc (rsmi_locate.cpp): where the shape has an rs_locate_kernel, that kernel runs in the place of
+// rs_verify_kernel and also ANDs the shards that explain each dirty tile into cand[b] (one word
+// per block, all-ones on the stream before the call; rplan: the ratio matrix's tables); fused
+// says whether it did.
+struct LocateFuse {
+    const RsPlanDev* rplan = nullptr;
+    uint32_t* cand = nullptr;
+    bool fused = false;
+};
 int launch_verify(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
                   const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks,
-                  uint32_t* bad, hipStream_t stream);
+                  uint32_t* bad, hipStream_t stream, LocateFuse* loc = nullptr);
+// One tile's rs_verify_kernel fn over nblocks blocks, or (rplan and cand given) its
+// rs_locate_kernel: one tile per wave unless waves_per_cu caps the grid, in launches whose tile
+// count fits 32 bits.
+int launch_stripe_tiles(rsmi_ctx* c, void* fn, const DevTile& t, const uint8_t* data, uint64_t data_rs,
+                        uint64_t data_bs, const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S,
+                        uint64_t nblocks, uint32_t* bad, const RsPlanDev* rplan, uint32_t* cand, hipStream_t stream);
+// The stream's entry of a per-stream scratch map (caller holds ctx->mu): verify_scratch, the
+// fallback's encoded rows; locate_scratch.  Past 32 streams the device is drained once and every
+// stream's scratch freed.
+rsmi_ctx::VerifyScratch& stream_scratch(std::map<hipStream_t, rsmi_ctx::VerifyScratch>& map, hipStream_t st);
+// What a host-memory call runs over stored stripes (Encoder.Verify, rsmi_locate): verify_host_impl
+// stages or uploads the rows on one of rsmi_verify_batch_host's three paths and calls
+//   prepare()  once, under ctx->mu with the device bound: the call's device result buffers
+//   launch()   per staged range of nb blocks from block b0, rows visible to the device
+//   fetch(st)  the results to the caller's memory: queued on st, which the caller then
+//              synchronises, or (st null, every stream idle) copied synchronously
+struct StripeCheck {
+    std::function<int()> prepare;
+    std::function<int(const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs, const uint8_t* parity,
+                      uint64_t parity_rs, uint64_t parity_bs, uint64_t nb, uint64_t b0, hipStream_t st)>
+        launch;
+    std::function<int(hipStream_t st)> fetch;
+};
+int verify_host_impl(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
+                     size_t parity_block_stride, size_t S, size_t nblocks, const StripeCheck& chk);
 int ensure_crc_tables(rsmi_ctx* c);
 int ensure_crc32_tables(rsmi_ctx* c);
 // R(row) / R32(row) of the rows the plan rebuilt (want && !present), one row per block at

@@ -3,6 +3,8 @@
 // the encode of the data rows produces?  The check reads k + m rows and writes only flags:
 // rs_verify_kernel (rs_verify_kernels.hip) over the tiles of the cached encode plan, or, for
 // shapes it is not built for, the encode into scratch followed by rs_compare_rows_kernel.
+// rsmi_locate (rsmi_locate.cpp) shares the launch (launch_verify with a LocateFuse) and the host
+// paths (verify_host_impl with its own StripeCheck).
 
 #include "rsmi_impl.hpp"
 
@@ -14,28 +16,51 @@ using namespace rsmi::impl;
 namespace rsmi {
 namespace impl {
 
-namespace {
-
-// The stream's scratch for the fallback's encoded rows (caller holds ctx->mu).  A caller that
-// cycles through many streams: past 32 of them the device is drained once and every stream's
-// scratch freed, as crc_scratch does.
-rsmi_ctx::VerifyScratch& verify_scratch(rsmi_ctx* c, hipStream_t st) {
-    auto it = c->verify_scratch.find(st);
-    if (it != c->verify_scratch.end()) return it->second;
-    if (c->verify_scratch.size() >= 32) {
+rsmi_ctx::VerifyScratch& stream_scratch(std::map<hipStream_t, rsmi_ctx::VerifyScratch>& map, hipStream_t st) {
+    auto it = map.find(st);
+    if (it != map.end()) return it->second;
+    if (map.size() >= 32) {
         (void)hipDeviceSynchronize();
-        for (auto& e : c->verify_scratch)
+        for (auto& e : map)
             if (e.second.p) (void)hipFree(e.second.p);
-        c->verify_scratch.clear();
+        map.clear();
     }
-    return c->verify_scratch[st];
+    return map[st];
 }
 
-}  // namespace
+int launch_stripe_tiles(rsmi_ctx* c, void* fn, const DevTile& t, const uint8_t* data, uint64_t data_rs,
+                        uint64_t data_bs, const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S,
+                        uint64_t nblocks, uint32_t* bad, const RsPlanDev* rplan, uint32_t* cand, hipStream_t stream) {
+    const uint64_t m = uint64_t(c->m);
+    const uint64_t cpb = (S + 15) / 16;
+    const uint64_t tpb = (cpb + uint64_t(kWave) - 1) / uint64_t(kWave);
+    constexpr int wpg = kFastWG / kWave;
+    long wg_cap = std::numeric_limits<long>::max();
+    if (c->opt_waves_per_cu > 0) wg_cap = std::max(1L, long(c->num_cu) * c->opt_waves_per_cu / wpg);
+    // split into launches whose tile count fits 32 bits
+    const uint64_t max_blocks = std::max<uint64_t>(1, (uint64_t(1) << 31) / tpb);
+    for (uint64_t b0 = 0; b0 < nblocks; b0 += max_blocks) {
+        const uint64_t nb = std::min(max_blocks, nblocks - b0);
+        uint32_t ntiles = uint32_t(nb * tpb);
+        uint32_t S32 = uint32_t(S), cpb32 = uint32_t(cpb), tpb32 = uint32_t(tpb), m32 = uint32_t(m);
+        const RsPlanDev* pd = t.dev;
+        const uint8_t* inb = data + b0 * data_bs;
+        const uint8_t* parb = parity + b0 * parity_bs;
+        uint32_t* badb = bad + b0 * m;
+        uint32_t* candb = cand ? cand + b0 : nullptr;
+        // rs_locate_kernel's parameters are rs_verify_kernel's and these two more
+        void* args[] = {&pd,  &inb,   &parb,  &data_bs, &data_rs, &parity_bs, &parity_rs, &S32,
+                        &cpb32, &tpb32, &ntiles,  &badb,    &m32,       &rplan,     &candb};
+        const uint64_t wgs = std::min<uint64_t>((ntiles + wpg - 1) / wpg, uint64_t(wg_cap));
+        HIP_TRY(hipLaunchKernel(fn, dim3(uint32_t(wgs)), dim3(uint32_t(wpg * kWave)), args, 0, stream));
+    }
+    return RSMI_OK;
+}
 
 int launch_verify(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
                   const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks,
-                  uint32_t* bad, hipStream_t stream) {
+                  uint32_t* bad, hipStream_t stream, LocateFuse* loc) {
+    if (loc) loc->fused = false;
     if (nblocks == 0 || S == 0) return RSMI_OK;
     const uint64_t m = uint64_t(c->m);
     HIP_TRY(hipMemsetAsync(bad, 0, nblocks * m * sizeof(uint32_t), stream));
@@ -48,33 +73,23 @@ int launch_verify(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t d
     for (const DevTile& t : plan.tiles)
         if (t.K > 16 || !(aligned ? verify_kernels().fn : verify_kernels().ua)[t.K][t.MT]) fast = false;
     if (fast) {
-        const uint64_t cpb = (S + 15) / 16;
-        const uint64_t tpb = (cpb + uint64_t(kWave) - 1) / uint64_t(kWave);
-        constexpr int wpg = kFastWG / kWave;
-        long wg_cap = std::numeric_limits<long>::max();
-        if (c->opt_waves_per_cu > 0) wg_cap = std::max(1L, long(c->num_cu) * c->opt_waves_per_cu / wpg);
-        // split into launches whose tile count fits 32 bits
-        const uint64_t max_blocks = std::max<uint64_t>(1, (uint64_t(1) << 31) / tpb);
+        // rsmi_locate: a one-tile plan whose shape has an rs_locate_kernel (2 <= m <= 4) runs it in
+        // the place of rs_verify_kernel, the same launch with the candidates formed as well
+        void* lfn = nullptr;
+        if (loc && plan.tiles.size() == 1)
+            lfn = (aligned ? locate_kernels().fn : locate_kernels().ua)[plan.tiles[0].K][plan.tiles[0].MT];
         std::string label;
         for (const DevTile& t : plan.tiles) {
-            void* fn = (aligned ? verify_kernels().fn : verify_kernels().ua)[t.K][t.MT];
-            for (uint64_t b0 = 0; b0 < nblocks; b0 += max_blocks) {
-                const uint64_t nb = std::min(max_blocks, nblocks - b0);
-                uint32_t ntiles = uint32_t(nb * tpb);
-                uint32_t S32 = uint32_t(S), cpb32 = uint32_t(cpb), tpb32 = uint32_t(tpb), m32 = uint32_t(m);
-                const RsPlanDev* pd = t.dev;
-                const uint8_t* inb = data + b0 * data_bs;
-                const uint8_t* parb = parity + b0 * parity_bs;
-                uint32_t* badb = bad + b0 * m;
-                void* args[] = {&pd,  &inb,   &parb,  &data_bs, &data_rs, &parity_bs, &parity_rs,
-                                &S32, &cpb32, &tpb32, &ntiles,  &badb,    &m32};
-                const uint64_t wgs = std::min<uint64_t>((ntiles + wpg - 1) / wpg, uint64_t(wg_cap));
-                HIP_TRY(hipLaunchKernel(fn, dim3(uint32_t(wgs)), dim3(uint32_t(wpg * kWave)), args, 0, stream));
-            }
+            void* fn = lfn ? lfn : (aligned ? verify_kernels().fn : verify_kernels().ua)[t.K][t.MT];
+            int rc = launch_stripe_tiles(c, fn, t, data, data_rs, data_bs, parity, parity_rs, parity_bs, S, nblocks, bad,
+                                         lfn ? loc->rplan : nullptr, lfn ? loc->cand : nullptr, stream);
+            if (rc) return rc;
             char buf[96];
-            std::snprintf(buf, sizeof buf, "rs_verify_kernel<K=%d,MT=%d>%s", t.K, t.MT, ua ? ",UA" : "");
+            std::snprintf(buf, sizeof buf, "rs_%s_kernel<K=%d,MT=%d>%s", lfn ? "locate" : "verify", t.K, t.MT,
+                          ua ? ",UA" : "");
             label = buf;
         }
+        if (loc) loc->fused = lfn != nullptr;
         set_last_kernel(c, label);
         return hip_status(hipGetLastError());
     }
@@ -84,7 +99,7 @@ int launch_verify(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t d
     // at most 64 MiB of scratch rows at a time.  The correctness path of rare shapes.
     const uint64_t Sp = round_up(S, 16);
     const uint64_t chunk = std::max<uint64_t>(1, (uint64_t(64) << 20) / (m * Sp));
-    rsmi_ctx::VerifyScratch& vs = verify_scratch(c, stream);
+    rsmi_ctx::VerifyScratch& vs = stream_scratch(c->verify_scratch, stream);
     int rc = reserve_on(vs.p, vs.cap, std::min(chunk, nblocks) * m * Sp, stream);
     if (rc) return rc;
     for (uint64_t b0 = 0; b0 < nblocks; b0 += chunk) {
@@ -106,21 +121,16 @@ int launch_verify(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t d
     return hip_status(hipGetLastError());
 }
 
-namespace {
-
-// Host-memory verify.  Page-locked data and parity (and option zero_copy): one kernel reads them
-// in place over PCIe, rows at pitch S.  Small pageable calls: the same kernel over the context's
-// page-locked staging, filled by CPU copies (the rule of encode_small).  Everything else: chunks
-// of about 64 MiB of device rows round-robin over the staging streams, so a chunk's upload runs
-// while the chunk before it is checked; rows at rsmi_recommended_pitch(S) for the aligned
-// kernel, as the host encode stages them.  There is no write-back leg: only the flags return,
-// in one copy at the end.
+// The host paths of Encoder.Verify and of rsmi_locate, which differ in chk alone (arguments
+// already checked, nblocks > 0).  Page-locked data and parity (and option
+// zero_copy): one kernel reads them in place over PCIe, rows at pitch S.  Small pageable calls:
+// the same kernel over the context's page-locked staging, filled by CPU copies (the rule of
+// encode_small).  Everything else: chunks of about 64 MiB of device rows round-robin over the
+// staging streams, so a chunk's upload runs while the chunk before it is checked; rows at
+// rsmi_recommended_pitch(S) for the aligned kernel, as the host encode stages them.  There is no
+// write-back leg: only the results return, in one copy at the end.
 int verify_host_impl(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
-                     size_t parity_block_stride, size_t S, size_t nblocks, uint32_t* bad_out) {
-    if (!c || !data || !parity || !bad_out) return RSMI_ERR_INVALID_ARG;
-    if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
-    if (data_block_stride < size_t(c->k) * S || parity_block_stride < size_t(c->m) * S) return RSMI_ERR_INVALID_ARG;
-    if (nblocks == 0) return RSMI_OK;
+                     size_t parity_block_stride, size_t S, size_t nblocks, const StripeCheck& chk) {
     std::lock_guard<std::mutex> g(c->mu);
     int rc = ensure_device(c);
     if (rc) return rc;
@@ -129,11 +139,7 @@ int verify_host_impl(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride,
     rc = encode_plan(c, plan);
     if (rc) return rc;
     const size_t k = size_t(c->k), m = size_t(c->m);
-    const size_t flag_bytes = nblocks * m * sizeof(uint32_t);
-    // the flags live in device memory on every path (no atomics aimed at host memory); every
-    // host call synchronises before it returns, so one buffer serves them all
-    if ((rc = reserve(c->d_vbad, c->vbad_cap, flag_bytes))) return rc;
-    uint32_t* d_bad = reinterpret_cast<uint32_t*>(c->d_vbad);
+    if ((rc = chk.prepare())) return rc;
 
     const size_t total = nblocks * (k + m) * S;
     const size_t data_len = (nblocks - 1) * data_block_stride + k * S;
@@ -162,8 +168,8 @@ int verify_host_impl(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride,
             }
             if (!zd || !zp) return RSMI_ERR_DEVICE;
         }
-        if ((rc = launch_verify(c, *plan, zd, S, dbs, zp, S, pbs, S, nblocks, d_bad, st))) return rc;
-        HIP_TRY(hipMemcpyAsync(bad_out, d_bad, flag_bytes, hipMemcpyDeviceToHost, st));
+        if ((rc = chk.launch(*plan, zd, S, dbs, zp, S, pbs, nblocks, 0, st))) return rc;
+        if ((rc = chk.fetch(st))) return rc;
         HIP_TRY(hipStreamSynchronize(st));
         return RSMI_OK;
     }
@@ -203,12 +209,42 @@ int verify_host_impl(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride,
         if ((rc = upload(st, st.d_in, in_bs, data + b0 * data_block_stride, data_block_stride, k, nb))) return rc;
         if ((rc = upload(st, st.d_out, par_bs, parity + b0 * parity_block_stride, parity_block_stride, m, nb)))
             return rc;
-        if ((rc = launch_verify(c, *plan, st.d_in, Sp, in_bs, st.d_out, Sp, par_bs, S, nb, d_bad + b0 * m, st.stream)))
-            return rc;
+        if ((rc = chk.launch(*plan, st.d_in, Sp, in_bs, st.d_out, Sp, par_bs, nb, b0, st.stream))) return rc;
     }
     for (int s = 0; s < ns; s++) HIP_TRY(hipStreamSynchronize(c->staging[s].stream));
-    HIP_TRY(hipMemcpy(bad_out, d_bad, flag_bytes, hipMemcpyDeviceToHost));
-    return RSMI_OK;
+    return chk.fetch(nullptr);
+}
+
+namespace {
+
+// Host-memory verify: the flags live in device memory on every path (no atomics aimed at host
+// memory); every host call synchronises before it returns, so one buffer serves them all.
+int verify_flags_host(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
+                      size_t parity_block_stride, size_t S, size_t nblocks, uint32_t* bad_out) {
+    if (!c || !data || !parity || !bad_out) return RSMI_ERR_INVALID_ARG;
+    if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
+    if (data_block_stride < size_t(c->k) * S || parity_block_stride < size_t(c->m) * S) return RSMI_ERR_INVALID_ARG;
+    if (nblocks == 0) return RSMI_OK;
+    const size_t m = size_t(c->m), flag_bytes = nblocks * m * sizeof(uint32_t);
+    uint32_t* d_bad = nullptr;
+    StripeCheck chk;
+    chk.prepare = [&]() -> int {
+        int rc = reserve(c->d_vbad, c->vbad_cap, flag_bytes);
+        d_bad = reinterpret_cast<uint32_t*>(c->d_vbad);
+        return rc;
+    };
+    chk.launch = [&](const Plan& plan, const uint8_t* d, uint64_t d_rs, uint64_t d_bs, const uint8_t* p, uint64_t p_rs,
+                     uint64_t p_bs, uint64_t nb, uint64_t b0, hipStream_t st) -> int {
+        return launch_verify(c, plan, d, d_rs, d_bs, p, p_rs, p_bs, S, nb, d_bad + b0 * m, st);
+    };
+    chk.fetch = [&](hipStream_t st) -> int {
+        if (st)
+            HIP_TRY(hipMemcpyAsync(bad_out, d_bad, flag_bytes, hipMemcpyDeviceToHost, st));
+        else
+            HIP_TRY(hipMemcpy(bad_out, d_bad, flag_bytes, hipMemcpyDeviceToHost));
+        return RSMI_OK;
+    };
+    return verify_host_impl(c, data, data_block_stride, parity, parity_block_stride, S, nblocks, chk);
 }
 
 }  // namespace
@@ -240,7 +276,7 @@ int rsmi_verify_batch_dev(rsmi_ctx* c, const uint8_t* d_data, size_t data_shard_
 
 int rsmi_verify_batch_host(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
                            size_t parity_block_stride, size_t S, size_t nblocks, uint32_t* bad_out) try {
-    return verify_host_impl(c, data, data_block_stride, parity, parity_block_stride, S, nblocks, bad_out);
+    return verify_flags_host(c, data, data_block_stride, parity, parity_block_stride, S, nblocks, bad_out);
 } catch (...) {
     return rsmi::impl::exception_status();
 }
@@ -250,7 +286,7 @@ int rsmi_verify(rsmi_ctx* c, const uint8_t* shards, size_t S, int* ok_out) try {
     if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
     const size_t k = size_t(c->k), m = size_t(c->m);
     std::vector<uint32_t> bad(m, 0);
-    int rc = verify_host_impl(c, shards, k * S, shards + k * S, m * S, S, 1, bad.data());
+    int rc = verify_flags_host(c, shards, k * S, shards + k * S, m * S, S, 1, bad.data());
     if (rc) return rc;
     *ok_out = std::all_of(bad.begin(), bad.end(), [](uint32_t x) { return x == 0; }) ? 1 : 0;
     return RSMI_OK;

@@ -32,6 +32,10 @@ ErrDevice = 100
 ErrNoDevice = 101
 ErrHost = 102
 
+# rsmi_locate verdicts that are not a shard index (include/rsmi.h RSMI_LOCATE_*)
+LocateClean = -1
+LocateUnknown = -2
+
 
 class RsmiError(Exception):
     def __init__(self, code: int, msg: str = ""):
@@ -87,6 +91,12 @@ def lib() -> ctypes.CDLL:
         "rsmi_verify_batch_host": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, u8p, c_size, c_size, c_size,
                                                   ctypes.c_void_p]),
         "rsmi_verify": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, ctypes.POINTER(ctypes.c_int)]),
+        "rsmi_locate_batch_dev": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, u8p, c_size, c_size, c_size, c_size,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+        "rsmi_locate_batch_host": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, u8p, c_size, c_size, c_size,
+                                                  ctypes.c_void_p, ctypes.c_void_p]),
+        "rsmi_locate": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, ctypes.POINTER(ctypes.c_int)]),
+        "rsmi_locate_matrix": (ctypes.c_int, [ctypes.c_void_p, u8p]),
         "rsmi_encode_block_coalesced": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, u8p, ctypes.c_void_p]),
         "rsmi_encode_block_coalesced_crcs": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, u8p, ctypes.c_void_p,
                                                             ctypes.c_void_p]),
@@ -217,6 +227,12 @@ class Codec:
         _check(lib().rsmi_decode_matrix(self._h, ctypes.addressof(_buf(p)), ctypes.addressof(_buf(out)), used))
         return bytes(out), list(used)
 
+    def locate_matrix(self) -> bytes:
+        """rsmi_locate_matrix: the m x k ratio matrix R[j][c] = M[k+j][c] / M[k][c], row-major."""
+        out = bytearray(self.m * self.k)
+        _check(lib().rsmi_locate_matrix(self._h, ctypes.addressof(_buf(out))))
+        return bytes(out)
+
     def set_option(self, key: str, value: int) -> None:
         _check(lib().rsmi_set_option(self._h, key.encode(), int(value)))
 
@@ -261,6 +277,21 @@ class Codec:
         """rsmi_verify_batch_host: bad_ptr[b*m + j] (uint32, host memory) non-zero iff parity row j
         of block b differs from the encode of the block's data rows."""
         _check(lib().rsmi_verify_batch_host(self._h, data_ptr, data_bs, parity_ptr, parity_bs, S, nblocks, bad_ptr))
+
+    def locate(self, shards, S: int) -> int:
+        """rsmi_locate of one block of n*S contiguous bytes: LocateClean, the index of the one
+        shard that explains the damage, or LocateUnknown."""
+        src = shards if isinstance(shards, bytearray) else bytearray(shards)
+        v = ctypes.c_int(LocateUnknown)
+        _check(lib().rsmi_locate(self._h, ctypes.addressof(_buf(src)) if src else None, S, ctypes.byref(v)))
+        return v.value
+
+    def locate_batch_host_ptr(self, data_ptr: int, data_bs: int, parity_ptr: int, parity_bs: int, S: int,
+                              nblocks: int, culprit_ptr: int, bad_ptr: int = 0) -> None:
+        """rsmi_locate_batch_host: culprit_ptr[b] (int32, host memory) and, when bad_ptr is given,
+        rsmi_verify_batch_host's flags."""
+        _check(lib().rsmi_locate_batch_host(self._h, data_ptr, data_bs, parity_ptr, parity_bs, S, nblocks,
+                                            culprit_ptr, bad_ptr or None))
 
     def reconstruct_batch_host_ptr(self, ptr: int, bs: int, S: int, nblocks: int, present: Sequence[bool],
                                    data_only: bool) -> None:
@@ -364,6 +395,13 @@ class Codec:
         non-zero iff stored parity row j of block b is not the encode of the block's data rows."""
         _check(lib().rsmi_verify_batch_dev(self._h, d_data, data_rs, data_bs, d_parity, parity_rs, parity_bs, S,
                                            nblocks, d_bad, stream or None))
+
+    def locate_batch_dev(self, d_data: int, data_rs: int, data_bs: int, d_parity: int, parity_rs: int,
+                         parity_bs: int, S: int, nblocks: int, d_culprit: int, d_bad: int = 0, stream: int = 0) -> None:
+        """rsmi_locate_batch_dev: d_culprit[b] (int32, device memory) and, when d_bad is given,
+        rsmi_verify_batch_dev's flags, from one pass over the rows."""
+        _check(lib().rsmi_locate_batch_dev(self._h, d_data, data_rs, data_bs, d_parity, parity_rs, parity_bs, S,
+                                           nblocks, d_culprit, d_bad or None, stream or None))
 
     def reconstruct_rows_batch_dev(self, d_shards: int, rs: int, bs: int, S: int, nblocks: int,
                                    present: Sequence[bool], required: Sequence[bool], stream: int = 0) -> None:
@@ -573,6 +611,17 @@ class Erasure:
         rc, S = check_shards([len(s) if s else 0 for s in shards], nil_ok=False)
         _check(rc)
         return self.encoder().verify(bytearray(b"".join(shards)), S)
+
+    def locate(self, shards: List[bytes]) -> int:
+        """Which shard breaks the stripe (rsmi_locate): LocateClean, the index of the one shard
+        whose replacement by its reconstruction makes the stripe clean, or LocateUnknown.  The
+        shard list is checked as verify checks it."""
+        n = self.data_blocks + self.parity_blocks
+        if len(shards) != n:
+            raise RsmiError(ErrTooFewShards)
+        rc, S = check_shards([len(s) if s else 0 for s in shards], nil_ok=False)
+        _check(rc)
+        return self.encoder().locate(bytearray(b"".join(shards)), S)
 
 
 def NewErasure(data_blocks: int, parity_blocks: int, block_size: int, device: int = 0) -> Erasure:

@@ -35,7 +35,9 @@ extern "C" {
  * rsmi_warm is new; the device-resident CRC entry points may run concurrently on different streams
  * of one context; rsmi_last_kernel returns a per-thread copy.
  * 5: the per-thread wait hook (rsmi_set_wait_hook, rsmi_run_wait_hook).  The Encoder.Verify entry
- * points (rsmi_verify, rsmi_verify_batch_host, rsmi_verify_batch_dev) joined version 5: additive. */
+ * points (rsmi_verify, rsmi_verify_batch_host, rsmi_verify_batch_dev) joined version 5: additive;
+ * so did the locate entry points (rsmi_locate, rsmi_locate_batch_host, rsmi_locate_batch_dev,
+ * rsmi_locate_matrix). */
 #define RSMI_ABI_VERSION 5
 
 typedef struct rsmi_ctx rsmi_ctx;
@@ -185,6 +187,52 @@ int rsmi_verify_batch_host(rsmi_ctx* ctx, const uint8_t* data, size_t data_block
 
 /* Encoder.Verify of one block: n*S contiguous bytes; *ok_out = 1 iff every parity row matches. */
 int rsmi_verify(rsmi_ctx* ctx, const uint8_t* shards, size_t S, int* ok_out);
+
+/* ------------------------------------------------------------------ locate: which shard is wrong */
+
+/* Verify says that a stripe's shards do not belong together; locate names the shard that breaks
+ * it, which no shard checksum can (a stale or swapped shard passes its own CRC).  A stripe is
+ * clean when every parity row equals the encode of the data rows over bytes [0, S); padding never
+ * counts.  Shard x (0..k+m-1) explains a dirty stripe when replacing row x by its reconstruction
+ * from the other rows yields a clean stripe.  The verdict of a block is
+ *   RSMI_LOCATE_CLEAN    the stripe is clean;
+ *   x in [0, k+m)        the stripe is dirty and shard x is the only shard that explains it;
+ *   RSMI_LOCATE_UNKNOWN  the stripe is dirty and no shard, or more than one, explains it.
+ * What the code's distance (m + 1) gives -- a property of the code, not of the implementation:
+ *   m = 1        every shard explains any damage, so a dirty stripe is always UNKNOWN;
+ *   m >= 2       a single damaged shard, however many of its bytes, is always named;
+ *   m >= 2t      t >= 2 damaged shards are always UNKNOWN;
+ *   beyond that  the damage can imitate a single other shard (its syndromes can be those of
+ *                that shard alone); the verdict is then that shard: it is the unique explanation.
+ * Every shard is taken as present (there are no missing-shard flags).  The calls are joined to ABI
+ * version 5 (additive); none of them takes or clears the per-thread wait hook. */
+#define RSMI_LOCATE_CLEAN (-1)
+#define RSMI_LOCATE_UNKNOWN (-2)
+
+/* Device-resident: layout, argument checks and fast-path alignment as rsmi_verify_batch_dev.  One
+ * pass over the k+m rows yields d_culprit_out[b] (device memory, nblocks verdicts) and, when
+ * d_bad_out is not NULL, d_bad_out[b*m + j], exactly rsmi_verify_batch_dev's flags.  Nothing else
+ * is written.  Stream-ordered, no sync (scratch is kept per stream; growing it waits for that
+ * stream once). */
+int rsmi_locate_batch_dev(rsmi_ctx* ctx, const uint8_t* d_data, size_t data_shard_stride, size_t data_block_stride,
+                          const uint8_t* d_parity, size_t parity_shard_stride, size_t parity_block_stride,
+                          size_t S, size_t nblocks, int32_t* d_culprit_out, uint32_t* d_bad_out, void* stream);
+
+/* Host memory, layout and the three paths of rsmi_verify_batch_host; culprit_out[b] and (when not
+ * NULL) bad_out[b*m + j] in host memory. */
+int rsmi_locate_batch_host(rsmi_ctx* ctx, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
+                           size_t parity_block_stride, size_t S, size_t nblocks, int32_t* culprit_out,
+                           uint32_t* bad_out);
+
+/* One block of n*S contiguous bytes: *culprit_out receives its verdict. */
+int rsmi_locate(rsmi_ctx* ctx, const uint8_t* shards, size_t S, int* culprit_out);
+
+/* Host-only, works without a GPU: the m x k ratio matrix R[j][c] = M[k+j][c] / M[k][c] of the
+ * encode matrix's parity rows (row 0 is all ones), row-major.  With syn_j = encode(data)_j ^
+ * stored parity_j, data shard c explains a byte column iff syn_j == R[j][c] * syn_0 for every
+ * j >= 1, and parity shard j iff syn_i == 0 for every i != j; the locate kernels' tables are
+ * built from R. */
+int rsmi_locate_matrix(const rsmi_ctx* ctx, uint8_t* out);
 
 /* Erasure.EncodeData for one block (same output as rsmi_encode_block, plus R(shard) in
  * raw_out[0..k+m) when raw_out is not NULL), coalesced with concurrent callers on the same
