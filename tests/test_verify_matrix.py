@@ -308,6 +308,38 @@ def test_fallback_long_row(gpu):
             assert np.array_equal(got, want), (pos, got)
 
 
+SEAM_HIT = [0, 65534, 65535, 65536, 2 ** 20 - 1, 2 ** 20, 2 ** 20 + 1, 2 ** 20 + 2]
+_SEAM = []
+
+
+def seam_stripes(rsmi):
+    """The layout of (b), shared with test_locate_matrix.py: (lay, full, fill).  RS(1,4), S = 15,
+    2^20 + 3 blocks of clean stripes from the SIMD oracle (spot-checked against the scalar one),
+    computed once and never written; fill(sh) is the byte buffer of lay that holds sh."""
+    k, m, S = 1, 4, 15
+    nb = 2 ** 20 + 3
+    assert m * ((S + 15) // 16 * 16) == 64 and (64 << 20) // 64 == 2 ** 20 < nb and SEAM_HIT[-1] == nb - 1
+    lay = Lay(rsmi, k, m, S, nb, False)
+    assert lay.rs == S and lay.bs == (k + m) * S and lay.off % 2 == 1
+    if not _SEAM:
+        rng = np.random.default_rng(4002)
+        data = rng.integers(0, 256, size=(nb, k, S), dtype=np.uint8)
+        par = orc.encode_fast(k, m, data)
+        for b in SEAM_HIT + [1, 77777, 2 ** 20 + 2]:  # the SIMD oracle against the scalar one
+            assert np.array_equal(orc.encode(k, m, data[b]), par[b]), b
+        full = np.concatenate([data, par], axis=1)
+        full.setflags(write=False)
+        _SEAM.append(full)
+
+    def fill(sh):  # Lay.fill without its per-row loop: this layout has no padding and no gaps
+        host = np.full(lay.size, GAP, dtype=np.uint8)
+        host[lay.off:lay.off + nb * lay.bs] = sh.reshape(-1)
+        assert np.array_equal(lay.rows(host)[nb - 1], sh[nb - 1])
+        return host
+
+    return lay, _SEAM[0], fill
+
+
 @pytest.mark.gpu
 def test_fallback_chunk_seam_and_y_loop(gpu):
     """(b) RS(1,4), S = 15, rows back to back at pitch 15 from an odd base, 2^20 + 3 blocks:
@@ -318,24 +350,9 @@ def test_fallback_chunk_seam_and_y_loop(gpu):
     torch, rsmi = gpu
     k, m, S = 1, 4, 15
     nb = 2 ** 20 + 3
-    assert m * ((S + 15) // 16 * 16) == 64 and (64 << 20) // 64 == 2 ** 20 < nb
     with _leg("leg4b"):
-        rng = np.random.default_rng(4002)
-        data = rng.integers(0, 256, size=(nb, k, S), dtype=np.uint8)
-        par = orc.encode_fast(k, m, data)
-        hit = [0, 65534, 65535, 65536, 2 ** 20 - 1, 2 ** 20, 2 ** 20 + 1, nb - 1]
-        for b in hit + [1, 77777, 2 ** 20 + 2]:  # the SIMD oracle against the scalar one
-            assert np.array_equal(orc.encode(k, m, data[b]), par[b]), b
-        lay = Lay(rsmi, k, m, S, nb, False)
-        assert lay.rs == S and lay.bs == (k + m) * S and lay.off % 2 == 1
-        full = np.concatenate([data, par], axis=1)
-
-        def fill(sh):  # Lay.fill without its per-row loop: this layout has no padding and no gaps
-            host = np.full(lay.size, GAP, dtype=np.uint8)
-            host[lay.off:lay.off + nb * lay.bs] = sh.reshape(-1)
-            assert np.array_equal(lay.rows(host)[nb - 1], sh[nb - 1])
-            return host
-
+        lay, full, fill = seam_stripes(rsmi)
+        hit = SEAM_HIT
         sh = full.copy()
         want = np.zeros((nb, m), dtype=bool)
         for i, b in enumerate(hit):
