@@ -176,6 +176,15 @@ const LocateKernelTable& locate_kernels();
 void* locate_verdict_kernel();
 void* locate_rows_kernel();
 
+// rsmi_heal (rs_heal_kernels.hip): rs_heal_kernel per (K, MT = m), the shapes of rs_locate_kernel,
+// and the byte-granular kernel of the fallback
+struct HealKernelTable {
+    void* fn[17][kMaxMT + 1];
+    void* ua[17][kMaxMT + 1];
+};
+const HealKernelTable& heal_kernels();
+void* heal_rows_kernel();
+
 // CRC-16 of shard rows (crc16.hpp): the device table buffer holds P[15][2][256] (the powers
 // A^(2^i), byte-sliced) and N[32][16] (u16); a wave folds kCrcSegTiles 1 KiB tiles of one row
 // with one N lookup per nibble (16-entry tables: each wave-wide lookup touches 8 distinct

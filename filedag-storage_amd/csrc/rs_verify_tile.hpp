@@ -4,6 +4,8 @@
 //   syn_j = encode(data)_j ^ stored parity_j
 // formed in registers and bad[block * m + parity row] raised where one is non-zero.  LOC: on a
 // tile with a non-zero syndrome the wave goes on to name the shards that explain it (locate_tile).
+// heal_tiles, the tile loop of rs_heal_kernel (rs_heal_kernels.hip), is built from the same pieces:
+// it forms the syndromes of the blocks a verdict names a shard in and rewrites that shard's row.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -186,6 +188,157 @@ __device__ __forceinline__ void stage_tables(u32x4* s_tbl, const RsPlanDev* plan
     if (rplan)
         for (int i = threadIdx.x; i < K * kColDwords; i += kFastWG) dst[K * kColDwords + i] = rplan->tbl[i];
     __syncthreads();
+}
+
+// The tile loop of rs_heal_kernel (rs_heal_kernels.hip): verify_tiles' walk, ring, loads and masks
+// over the blocks whose verdict names a shard x (verdict[block] >= 0, rsmi_locate's), and in the
+// place of the flags the one row store that makes the stripe clean:
+//   parity shard x = K + j   row ^= syn_j                  (= encode(data)_j)
+//   data shard x             row ^= inv(M[0][x]) * syn_0   (syn_0 = M[0][x] * the row's error)
+// The row's old bytes are those of the load the syndromes came from: a parity chunk is still in
+// the ring (or in xs), a data chunk is kept as it passes through the column loop (before_col).
+// No byte is loaded twice, so on UA layouts, where the row's last window overlaps the one before
+// it and the two may belong to different waves, the update is idempotent per byte: a byte another
+// wave has healed already gives a zero syndrome and stays, an unhealed one gives the same delta in
+// both waves.  rtbl: the ratio plan's tables, whose output slot 0 holds inv(M[0][c]).  A tile of a
+// block with a negative verdict loads nothing; a lane past the row's last chunk, a lane whose
+// delta is zero and a tile where every delta is zero store nothing; an aligned row's last, partial
+// chunk is stored as dwords, then bytes (store_rows_aligned), so no byte at or past S is written.
+// s_tbl is staged here, and only by a workgroup with a tile to heal.
+template <int K, int MT, bool UA>
+__device__ __forceinline__ void heal_tiles(u32x4* s_tbl, const RsPlanDev* __restrict__ plan,
+                                           const RsPlanDev* __restrict__ rplan, uint8_t* in, uint8_t* par,
+                                           uint64_t in_bs, uint64_t in_rs, uint64_t par_bs, uint64_t par_rs,
+                                           uint32_t S, uint32_t cpb, uint32_t tpb, uint32_t ntiles,
+                                           const int32_t* __restrict__ verdict) {
+    constexpr uint32_t kWavesPerWG = kFastWG / kWave;
+    const uint32_t lane = threadIdx.x & (kWave - 1);
+    const uint32_t wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+    const uint32_t nw = gridDim.x * kWavesPerWG;
+    const uint32_t wg =
+        UA ? tile_group(blockIdx.x, gridDim.x, (gridDim.x & 7u) ? 0u : gridDim.x) : uint32_t(blockIdx.x);
+    uint32_t t = wg * kWavesPerWG + wid;
+
+    // one scalar load per tile of the wave (one tile, unless waves_per_cu caps the grid): a
+    // workgroup with nothing to heal ends here, before the tables and before any row load
+    int work = 0;
+    for (uint32_t u = t; u < ntiles; u += nw) work |= int(verdict[u / tpb] >= 0);
+    if (!__syncthreads_or(work)) return;
+    stage_tables<K>(s_tbl, plan, rplan);
+    if (!work) return;
+
+    constexpr int P = rows_in_flight<K, MT>();
+    constexpr int PR = MT < P ? MT : P;
+    uint64_t in_off[K], par_off[MT];
+#pragma unroll
+    for (int c = 0; c < K; c++) in_off[c] = uint64_t(plan->in_row[c]) * in_rs;
+#pragma unroll
+    for (int j = 0; j < MT; j++) par_off[j] = uint64_t(plan->out_row[j]) * par_rs;
+
+    for (TileWalk tw(t, nw, tpb); t < ntiles; t += nw, tw.next(tpb)) {
+        const uint32_t blk = tw.blk;
+        const int32_t vd = __builtin_amdgcn_readfirstlane(verdict[blk]);
+        if (vd < 0 || vd >= K + MT) continue;
+        const uint32_t xr = uint32_t(vd);  // the culprit row, wave-uniform
+        uint8_t* ib = in + uint64_t(blk) * in_bs;
+        uint8_t* pb = par + uint64_t(blk) * par_bs;
+        const LaneChunk lc = lane_chunk<UA>(tw.tib, lane, cpb, S);
+        const uint32_t ch = lc.ch, chl = lc.chl, win = lc.win;
+        uint32_t mk[4];
+        {
+            const int valid = ch < cpb ? (UA ? 16 : int(S) - int(ch * 16u)) : 0;
+#pragma unroll
+            for (int w = 0; w < 4; w++) mk[w] = bytes_mask(valid - 4 * w);
+        }
+        auto load_col = [&](int c) {
+            if constexpr (UA)
+                return ld16u<true>(ib + in_off[c] + win);
+            else
+                return ld16<true>(reinterpret_cast<const u32x4*>(ib + in_off[c]) + chl);
+        };
+        auto load_par = [&](int j) {
+            if constexpr (UA)
+                return ld16u<true>(pb + par_off[j] + win);
+            else
+                return ld16<true>(reinterpret_cast<const u32x4*>(pb + par_off[j]) + chl);
+        };
+
+        u32x4 v[P];
+        u32x4 xs[MT > PR ? MT - PR : 1];
+#pragma unroll
+        for (int c = 0; c < P; c++) v[c] = load_col(c);
+#pragma unroll
+        for (int j = PR; j < MT; j++) xs[j - PR] = load_par(j);
+
+        uint32_t acc[MT][4];
+        u32x4 old = {0u, 0u, 0u, 0u};  // the culprit row's chunk as loaded
+        gf_tile_columns<K, MT, P>(
+            s_tbl, v, acc,
+            [&](int c, u32x4& x) {
+                // decided here, column by column: left to the compiler the K selects sink below the
+                // loop and every row stays live until then
+                if (uint32_t(c) == xr) old = x;
+                asm volatile("" : "+v"(old));
+            },
+            GfNone{}, GfNone{},
+            [&](int c, u32x4& x) {
+                if (c + P < K)
+                    x = load_col(c + P);
+                else if (c + P - K < PR)
+                    x = load_par(c + P - K);
+            });
+
+        uint32_t syn0[4], delta[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int j = 0; j < MT; j++) {
+            const u32x4 sp = j < PR ? v[(K - P + j) % P] : xs[j < PR ? 0 : j - PR];
+            uint32_t syn[4];
+#pragma unroll
+            for (int w = 0; w < 4; w++) syn[w] = (acc[j][w] ^ u4get(sp, w)) & mk[w];
+            if (j == 0) {
+#pragma unroll
+                for (int w = 0; w < 4; w++) syn0[w] = syn[w];
+            }
+            if (xr == uint32_t(K + j)) {
+                old = sp;
+#pragma unroll
+                for (int w = 0; w < 4; w++) delta[w] = syn[w];
+            }
+        }
+        uint8_t* row;
+        if (xr < uint32_t(K)) {
+            // inv(M[0][x]) * syn_0: the three-v_perm multiply, the column's tables from LDS
+            const u32x4* rt = s_tbl + K * (kColDwords / 4) + xr * 5u;
+            u32x4 T[5];
+#pragma unroll
+            for (int f = 0; f < 5; f++) T[f] = rt[f];
+#pragma unroll
+            for (int w = 0; w < 4; w++) {
+                const uint32_t s1 = syn0[w] & 0x07070707u;
+                const uint32_t s2 = (syn0[w] >> 3) & 0x07070707u;
+                const uint32_t s3 = (syn0[w] >> 6) & 0x03030303u;
+                const uint32_t p1 = __builtin_amdgcn_perm(u4get(T[1], 0), u4get(T[0], 0), s1);
+                const uint32_t p2 = __builtin_amdgcn_perm(u4get(T[3], 0), u4get(T[2], 0), s2);
+                const uint32_t p3 = __builtin_amdgcn_perm(u4get(T[4], 0), u4get(T[4], 0), s3);
+                delta[w] = xor3(p1, p2, p3);
+            }
+            row = ib + uint64_t(plan->in_row[xr]) * in_rs;
+        } else {
+            row = pb + uint64_t(plan->out_row[xr - uint32_t(K)]) * par_rs;
+        }
+        const bool mine = (delta[0] | delta[1] | delta[2] | delta[3]) != 0u;
+        if (__builtin_amdgcn_ballot_w64(mine) == 0ull) continue;
+        if (mine && ch < cpb) {
+            const uint32_t fix[1][4] = {
+                {u4get(old, 0) ^ delta[0], u4get(old, 1) ^ delta[1], u4get(old, 2) ^ delta[2], u4get(old, 3) ^ delta[3]}};
+            if constexpr (UA) {
+                st16u<false>(row + win, u32x4{fix[0][0], fix[0][1], fix[0][2], fix[0][3]});
+            } else {
+                const uint64_t off[1] = {0};
+                store_rows_aligned<0, 1>(row, off, ch, S, fix);
+            }
+        }
+    }
 }
 
 }  // namespace rsmi

@@ -5,9 +5,10 @@
 //   rsmi_coalesce.cpp  group commit of concurrent single-block calls
 //   rsmi_verify.cpp    Encoder.Verify: stored parity checked against the data rows
 //   rsmi_locate.cpp    rsmi_locate: the shard that breaks a stripe, from Verify's syndromes
+//   rsmi_heal.cpp      rsmi_heal: locate, then the named shard rewritten on the same stream
 // No CPU compute path anywhere: every byte of parity, reconstructed data or CRC and every verify
 // flag comes out of the HIP kernels (rs_kernels.hip, rs_kernels_tb.hip, rs_crc16_kernels.hip, rs_crc32_kernels.hip,
-// rs_verify_kernels.hip, rs_locate_kernels.hip).
+// rs_verify_kernels.hip, rs_locate_kernels.hip, rs_heal_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -298,15 +299,33 @@ rsmi_ctx::VerifyScratch& stream_scratch(std::map<hipStream_t, rsmi_ctx::VerifySc
 //   launch()   per staged range of nb blocks from block b0, rows visible to the device
 //   fetch(st)  the results to the caller's memory: queued on st, which the caller then
 //              synchronises, or (st null, every stream idle) copied synchronously
+// rsmi_heal alone writes rows, so it alone sets the write-back leg (unset: no step is added):
+//   small_done(sd, sp)          the small staged call, after its synchronisation: the page-locked
+//                               copies of the data blocks (k*S apart) and of the parity blocks
+//                               (m*S apart), null for a half that was not staged
+//   chunk_done(st, b0, nb, Sp)  the upload pipeline, before st's device rows (pitch Sp) of blocks
+//                               b0 .. b0+nb are overwritten by a later chunk, and at the end
 struct StripeCheck {
     std::function<int()> prepare;
     std::function<int(const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs, const uint8_t* parity,
                       uint64_t parity_rs, uint64_t parity_bs, uint64_t nb, uint64_t b0, hipStream_t st)>
         launch;
     std::function<int(hipStream_t st)> fetch;
+    std::function<int(const uint8_t* sd, const uint8_t* sp)> small_done;
+    std::function<int(Staging& st, uint64_t b0, uint64_t nb, size_t Sp)> chunk_done;
 };
 int verify_host_impl(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
                      size_t parity_block_stride, size_t S, size_t nblocks, const StripeCheck& chk);
+// rsmi_locate of nblocks blocks (rsmi_locate.cpp; caller holds ctx->mu): verdicts culprit[b] and,
+// when bad is given, Verify's flags, device memory, stream-ordered.  fused: whether rs_locate_kernel
+// ran (false: m = 1, or the encode into scratch and rs_locate_rows_kernel).
+int launch_locate(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
+                  const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks,
+                  int32_t* culprit, uint32_t* bad, hipStream_t stream, bool* fused = nullptr);
+// the ratio matrix's plan "L" (output slot 0: inv(M[k][c])) and the byte-granular kernels' tables
+// (ctx->d_locate_tbl: log | exp | R | inv(M[k][c])), both built on first use
+int ratio_plan(rsmi_ctx* c, std::shared_ptr<Plan>& out);
+int ensure_locate_tables(rsmi_ctx* c);
 int ensure_crc_tables(rsmi_ctx* c);
 int ensure_crc32_tables(rsmi_ctx* c);
 // R(row) / R32(row) of the rows the plan rebuilt (want && !present), one row per block at

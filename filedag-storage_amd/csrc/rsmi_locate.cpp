@@ -27,7 +27,11 @@ bool locate_ratios(const rsmi_ctx* c, Matrix& R) {
     return true;
 }
 
-// the v_perm tables of R, laid out as the encode plan's (cached beside it)
+}  // namespace
+
+// the v_perm tables of R, laid out as the encode plan's (cached beside it).  Row 0 of R is all
+// ones and no locate kernel reads its tables (locate_tile starts at row 1), so output slot 0
+// carries inv(M[k][c]) instead, the factor rs_heal_kernel turns syn_0 into a data row's error with
 int ratio_plan(rsmi_ctx* c, std::shared_ptr<Plan>& out) {
     auto it = c->plans.find("L");
     if (it != c->plans.end()) {
@@ -36,6 +40,7 @@ int ratio_plan(rsmi_ctx* c, std::shared_ptr<Plan>& out) {
     }
     Matrix R;
     if (!locate_ratios(c, R)) return RSMI_ERR_SINGULAR;
+    for (int col = 0; col < c->k; col++) R.at(0, col) = gf().div(1, c->M.at(c->k, col));
     std::vector<int> in_rows(c->k), out_rows(c->m);
     for (int i = 0; i < c->k; i++) in_rows[i] = i;
     for (int j = 0; j < c->m; j++) out_rows[j] = j;
@@ -44,15 +49,17 @@ int ratio_plan(rsmi_ctx* c, std::shared_ptr<Plan>& out) {
     return rc;
 }
 
-// rs_locate_rows_kernel's tables: log[256] | exp[512] | R[m][k]
+// rs_locate_rows_kernel's tables: log[256] | exp[512] | R[m][k], and behind them
+// rs_heal_rows_kernel's inv(M[k][c])[k]
 int ensure_locate_tables(rsmi_ctx* c) {
     if (c->d_locate_tbl) return RSMI_OK;
     Matrix R;
     if (!locate_ratios(c, R)) return RSMI_ERR_SINGULAR;
-    std::vector<uint8_t> h(768 + R.v.size());
+    std::vector<uint8_t> h(768 + R.v.size() + size_t(c->k));
     std::memcpy(h.data(), gf().log.data(), 256);
     std::memcpy(h.data() + 256, gf().exp.data(), 512);
     std::memcpy(h.data() + 768, R.v.data(), R.v.size());
+    for (int col = 0; col < c->k; col++) h[768 + R.v.size() + size_t(col)] = gf().div(1, c->M.at(c->k, col));
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_locate_tbl), h.size()));
     HIP_TRY(hipMemcpy(c->d_locate_tbl, h.data(), h.size(), hipMemcpyHostToDevice));
     return RSMI_OK;
@@ -60,10 +67,12 @@ int ensure_locate_tables(rsmi_ctx* c) {
 
 // Locate of nblocks blocks (caller holds ctx->mu, the device is bound): culprit[b] and, when bad
 // is given, Verify's flags bad[b*m + j], both device memory.  Stream-ordered; the candidate words
-// (and the flags, when the caller takes none) live in the stream's scratch.
+// (and the flags, when the caller takes none) live in the stream's scratch.  fused (rsmi_heal.cpp):
+// whether rs_locate_kernel ran (false: m = 1 or the fallback).
 int launch_locate(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
                   const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks,
-                  int32_t* culprit, uint32_t* bad, hipStream_t stream) {
+                  int32_t* culprit, uint32_t* bad, hipStream_t stream, bool* fused) {
+    if (fused) *fused = false;
     if (nblocks == 0 || S == 0) return RSMI_OK;
     const uint64_t k = uint64_t(c->k), m = uint64_t(c->m);
     uint32_t n32 = uint32_t(c->n), m32 = uint32_t(m), words = (n32 + 31u) / 32u;
@@ -93,6 +102,7 @@ int launch_locate(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t d
         if ((rc = launch_verify(c, plan, data, data_rs, data_bs, parity, parity_rs, parity_bs, S, nblocks, bad, stream,
                                 rp ? &loc : nullptr)))
             return rc;
+        if (fused) *fused = loc.fused;
         if (!loc.fused) {
             // m > 4, K > 16 or not instantiated, unaligned rows shorter than 16 bytes: Verify's
             // launch gave the flags; now the parity rows encoded into scratch (as Verify's own
@@ -131,6 +141,8 @@ int launch_locate(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t d
                             stream));
     return hip_status(hipGetLastError());
 }
+
+namespace {
 
 // Host-memory locate on Verify's host paths (verify_host_impl): flags and verdicts live in the
 // context's device result buffer, flags first.

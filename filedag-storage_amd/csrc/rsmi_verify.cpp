@@ -127,8 +127,9 @@ int launch_verify(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t d
 // the same kernel over the context's page-locked staging, filled by CPU copies (the rule of
 // encode_small).  Everything else: chunks of about 64 MiB of device rows round-robin over the
 // staging streams, so a chunk's upload runs while the chunk before it is checked; rows at
-// rsmi_recommended_pitch(S) for the aligned kernel, as the host encode stages them.  There is no
-// write-back leg: only the results return, in one copy at the end.
+// rsmi_recommended_pitch(S) for the aligned kernel, as the host encode stages them.  Verify and
+// locate have no write-back leg: only the results return, in one copy at the end.  rsmi_heal's
+// (chk.small_done, chk.chunk_done) returns the rows it rewrote and nothing else.
 int verify_host_impl(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
                      size_t parity_block_stride, size_t S, size_t nblocks, const StripeCheck& chk) {
     std::lock_guard<std::mutex> g(c->mu);
@@ -171,6 +172,10 @@ int verify_host_impl(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride,
         if ((rc = chk.launch(*plan, zd, S, dbs, zp, S, pbs, nblocks, 0, st))) return rc;
         if ((rc = chk.fetch(st))) return rc;
         HIP_TRY(hipStreamSynchronize(st));
+        if (chk.small_done && in_sz + par_sz) {
+            const uint8_t* hs = c->h_small;
+            return chk.small_done(in_sz ? hs : nullptr, par_sz ? hs + in_sz : nullptr);
+        }
         return RSMI_OK;
     }
 
@@ -200,9 +205,22 @@ int verify_host_impl(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride,
         }
         return RSMI_OK;
     };
+    // the write-back leg (rsmi_heal): the chunk a staging slot holds is owed its chunk_done before
+    // the slot's rows are reused, the last chunks at the end
+    struct Owed {
+        size_t b0 = 0, nb = 0;
+    } owed[3];
+    auto settle = [&](int s) -> int {
+        const Owed o = owed[s];
+        owed[s] = Owed{};
+        return chk.chunk_done && o.nb ? chk.chunk_done(c->staging[s], o.b0, o.nb, Sp) : RSMI_OK;
+    };
     for (size_t b0 = 0, i = 0; b0 < nblocks; b0 += chunk, i++) {
         Staging& st = c->staging[i % ns];
         const size_t nb = std::min(chunk, nblocks - b0);
+        if ((rc = settle(int(i % ns)))) return rc;
+        owed[i % ns].b0 = b0;
+        owed[i % ns].nb = nb;
         if ((rc = reserve_on(st.d_in, st.in_cap, nb * in_bs, st.stream))) return rc;
         if ((rc = reserve_on(st.d_out, st.out_cap, nb * par_bs, st.stream))) return rc;
         if (!d2 && (rc = reserve_on(st.d_lin, st.lin_cap, nb * std::max(k, m) * S, st.stream))) return rc;
@@ -211,6 +229,8 @@ int verify_host_impl(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride,
             return rc;
         if ((rc = chk.launch(*plan, st.d_in, Sp, in_bs, st.d_out, Sp, par_bs, nb, b0, st.stream))) return rc;
     }
+    for (int s = 0; s < ns; s++)
+        if ((rc = settle(s))) return rc;
     for (int s = 0; s < ns; s++) HIP_TRY(hipStreamSynchronize(c->staging[s].stream));
     return chk.fetch(nullptr);
 }

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RSMI_LIB: a diagnostic build of the library (tools/Makefile variants) for A/B runs
@@ -97,6 +97,11 @@ def lib() -> ctypes.CDLL:
                                                   ctypes.c_void_p, ctypes.c_void_p]),
         "rsmi_locate": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, ctypes.POINTER(ctypes.c_int)]),
         "rsmi_locate_matrix": (ctypes.c_int, [ctypes.c_void_p, u8p]),
+        "rsmi_heal_batch_dev": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, u8p, c_size, c_size, c_size, c_size,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+        "rsmi_heal_batch_host": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, u8p, c_size, c_size, c_size,
+                                                ctypes.c_void_p, ctypes.c_void_p]),
+        "rsmi_heal": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, ctypes.POINTER(ctypes.c_int)]),
         "rsmi_encode_block_coalesced": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, u8p, ctypes.c_void_p]),
         "rsmi_encode_block_coalesced_crcs": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, u8p, ctypes.c_void_p,
                                                             ctypes.c_void_p]),
@@ -293,6 +298,23 @@ class Codec:
         _check(lib().rsmi_locate_batch_host(self._h, data_ptr, data_bs, parity_ptr, parity_bs, S, nblocks,
                                             culprit_ptr, bad_ptr or None))
 
+    def heal(self, shards: bytearray, S: int) -> int:
+        """rsmi_heal of one block of n*S contiguous bytes, healed in place: the verdict of the
+        block as it was (rsmi_locate's); when it names a shard, that row of shards is rewritten
+        so that the stripe is clean, and nothing else is."""
+        if not isinstance(shards, bytearray):
+            raise TypeError("heal rewrites its argument: pass a bytearray")
+        v = ctypes.c_int(LocateUnknown)
+        _check(lib().rsmi_heal(self._h, ctypes.addressof(_buf(shards)) if shards else None, S, ctypes.byref(v)))
+        return v.value
+
+    def heal_batch_host_ptr(self, data_ptr: int, data_bs: int, parity_ptr: int, parity_bs: int, S: int,
+                            nblocks: int, culprit_ptr: int, bad_ptr: int = 0) -> None:
+        """rsmi_heal_batch_host: rsmi_locate_batch_host's outputs, and the named row of every block
+        that has one rewritten in the caller's buffers."""
+        _check(lib().rsmi_heal_batch_host(self._h, data_ptr, data_bs, parity_ptr, parity_bs, S, nblocks,
+                                          culprit_ptr, bad_ptr or None))
+
     def reconstruct_batch_host_ptr(self, ptr: int, bs: int, S: int, nblocks: int, present: Sequence[bool],
                                    data_only: bool) -> None:
         p = bytearray(1 if x else 0 for x in present)
@@ -402,6 +424,13 @@ class Codec:
         rsmi_verify_batch_dev's flags, from one pass over the rows."""
         _check(lib().rsmi_locate_batch_dev(self._h, d_data, data_rs, data_bs, d_parity, parity_rs, parity_bs, S,
                                            nblocks, d_culprit, d_bad or None, stream or None))
+
+    def heal_batch_dev(self, d_data: int, data_rs: int, data_bs: int, d_parity: int, parity_rs: int,
+                       parity_bs: int, S: int, nblocks: int, d_culprit: int, d_bad: int = 0, stream: int = 0) -> None:
+        """rsmi_heal_batch_dev: rsmi_locate_batch_dev's outputs, then, behind them on the stream,
+        the named row of every block that has one rewritten so that the stripe is clean."""
+        _check(lib().rsmi_heal_batch_dev(self._h, d_data, data_rs, data_bs, d_parity, parity_rs, parity_bs, S,
+                                         nblocks, d_culprit, d_bad or None, stream or None))
 
     def reconstruct_rows_batch_dev(self, d_shards: int, rs: int, bs: int, S: int, nblocks: int,
                                    present: Sequence[bool], required: Sequence[bool], stream: int = 0) -> None:
@@ -622,6 +651,23 @@ class Erasure:
         rc, S = check_shards([len(s) if s else 0 for s in shards], nil_ok=False)
         _check(rc)
         return self.encoder().locate(bytearray(b"".join(shards)), S)
+
+    def heal(self, shards: List[bytes]) -> Tuple[int, List[bytes]]:
+        """Locate, then rewrite the named shard (rsmi_heal): (verdict, shards), the verdict that of
+        locate for the list as given; when it names a shard, that entry of the returned list is
+        its reconstruction from the others, every other entry is the caller's.  The shard list is
+        checked as verify checks it."""
+        n = self.data_blocks + self.parity_blocks
+        if len(shards) != n:
+            raise RsmiError(ErrTooFewShards)
+        rc, S = check_shards([len(s) if s else 0 for s in shards], nil_ok=False)
+        _check(rc)
+        buf = bytearray(b"".join(shards))
+        v = self.encoder().heal(buf, S)
+        out = list(shards)
+        if v >= 0:
+            out[v] = bytes(buf[v * S:(v + 1) * S])
+        return v, out
 
 
 def NewErasure(data_blocks: int, parity_blocks: int, block_size: int, device: int = 0) -> Erasure:

@@ -37,7 +37,8 @@ extern "C" {
  * 5: the per-thread wait hook (rsmi_set_wait_hook, rsmi_run_wait_hook).  The Encoder.Verify entry
  * points (rsmi_verify, rsmi_verify_batch_host, rsmi_verify_batch_dev) joined version 5: additive;
  * so did the locate entry points (rsmi_locate, rsmi_locate_batch_host, rsmi_locate_batch_dev,
- * rsmi_locate_matrix). */
+ * rsmi_locate_matrix) and the heal entry points (rsmi_heal, rsmi_heal_batch_host,
+ * rsmi_heal_batch_dev). */
 #define RSMI_ABI_VERSION 5
 
 typedef struct rsmi_ctx rsmi_ctx;
@@ -233,6 +234,48 @@ int rsmi_locate(rsmi_ctx* ctx, const uint8_t* shards, size_t S, int* culprit_out
  * j >= 1, and parity shard j iff syn_i == 0 for every i != j; the locate kernels' tables are
  * built from R. */
 int rsmi_locate_matrix(const rsmi_ctx* ctx, uint8_t* out);
+
+/* ------------------------------------------------------------------ heal: rewrite the shard that is wrong */
+
+/* Locate names the shard that breaks a stripe; heal goes on, on the same stream and with no host
+ * round trip in between, to rewrite it, so a scrub needs no sort of the blocks by culprit and no
+ * reconstruct call per erasure pattern: every dirty block may have its own culprit.
+ *   Outputs.  culprit_out[b] and the optional bad_out are exactly what rsmi_locate_* returns for
+ *   the stripes as they were before the call.
+ *   What is written.  In every block whose verdict is a shard x in [0, k+m), bytes [0, S) of row x
+ *   are rewritten so that the stripe is clean: the new row is the reconstruction of row x from the
+ *   other rows.  Blocks whose verdict is RSMI_LOCATE_CLEAN or RSMI_LOCATE_UNKNOWN are not written
+ *   at all.  No row other than x is written, no byte at or past S of any row, no byte of a gap:
+ *   the layout contract holds, padding may be read and is never written.  m = 1 never heals: a
+ *   dirty stripe there is always UNKNOWN.
+ *   What the code's distance (m + 1) gives -- a property of the code, not of the implementation:
+ *   with at most m - 1 damaged shards in a block a named shard is the only damaged one, and the
+ *   heal restores the original bytes.  With m or more damaged shards the damage can imitate a
+ *   single other shard (see locate above); the heal then rewrites that shard: the stripe becomes
+ *   a clean codeword, but not the original one.  Callers that cannot bound the damage keep the
+ *   shard checksums as the second witness.
+ *   Overlap.  The data and parity halves must not overlap each other.
+ * Argument checks and statuses are those of rsmi_locate_*.  The calls are joined to ABI version 5
+ * (additive); none of them takes or clears the per-thread wait hook. */
+
+/* Device-resident: layout, argument checks and fast-path alignment as rsmi_locate_batch_dev.
+ * Stream-ordered, no sync: d_culprit_out is written by the locate launches and read by the heal
+ * launch behind them on the stream (scratch is kept per stream; growing it waits for that stream
+ * once). */
+int rsmi_heal_batch_dev(rsmi_ctx* ctx, uint8_t* d_data, size_t data_shard_stride, size_t data_block_stride,
+                        uint8_t* d_parity, size_t parity_shard_stride, size_t parity_block_stride, size_t S,
+                        size_t nblocks, int32_t* d_culprit_out, uint32_t* d_bad_out, void* stream);
+
+/* Host memory, layout and the three paths of rsmi_verify_batch_host; culprit_out[b] and (when not
+ * NULL) bad_out[b*m + j] in host memory.  Page-locked data and parity are healed where they lie,
+ * by kernel stores over PCIe; from the staging of a small call and from the device rows of the
+ * upload pipeline the rewritten rows are copied back to the caller's buffers, and nothing else. */
+int rsmi_heal_batch_host(rsmi_ctx* ctx, uint8_t* data, size_t data_block_stride, uint8_t* parity,
+                         size_t parity_block_stride, size_t S, size_t nblocks, int32_t* culprit_out,
+                         uint32_t* bad_out);
+
+/* One block of n*S contiguous bytes, healed in place: *culprit_out receives its verdict. */
+int rsmi_heal(rsmi_ctx* ctx, uint8_t* shards, size_t S, int* culprit_out);
 
 /* Erasure.EncodeData for one block (same output as rsmi_encode_block, plus R(shard) in
  * raw_out[0..k+m) when raw_out is not NULL), coalesced with concurrent callers on the same
