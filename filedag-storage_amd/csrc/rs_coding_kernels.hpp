@@ -119,11 +119,14 @@ __device__ __forceinline__ void launch_done(const BasesArg<TB>& bases) {
 // TB: the blocks lie where a table of block bases says (BlockBases: a coalesced group of callers'
 // own page-locked buffers, one launch for the group); in / out are offsets from each base.
 // ST: how the aligned form stores its output rows (store_policy, rs_plan.hpp): 0 plain, 1
-// nontemporal, n >= 2 nontemporal but the last n - 1 rows plain.  The default is what NT says, and
-// the launch label prints NT alone.
+// nontemporal, n >= 2 nontemporal but the last n - 1 rows plain, -1 write-through.  The default is
+// what NT says, and the launch label prints NT alone.
+// WMAX: at most this many waves per SIMD (waves_cap, rs_plan.hpp; 0: no cap).  The attribute stands
+// before the launch bounds, which would override it.
 template <int K, int MT, int NT, int WPS = kMinWavesPerSimd, bool UA = false, bool CRC = false, bool TB = false,
-          int ST = (NT == 1 ? 1 : 0)>
-__global__ __launch_bounds__(kFastWG, WPS) void rs_fast_kernel(const RsPlanDev* __restrict__ plan,
+          int ST = (NT == 1 ? 1 : 0), int WMAX = 0>
+__global__ __attribute__((amdgpu_waves_per_eu(WPS, WMAX)))
+__launch_bounds__(kFastWG, WPS) void rs_fast_kernel(const RsPlanDev* __restrict__ plan,
                                                        const uint8_t* __restrict__ in, uint8_t* __restrict__ out,
                                                        uint64_t in_bs, uint64_t in_rs, uint64_t out_bs,
                                                        uint64_t out_rs, uint32_t S, uint32_t cpb, uint32_t tpb,
@@ -132,7 +135,8 @@ __global__ __launch_bounds__(kFastWG, WPS) void rs_fast_kernel(const RsPlanDev* 
                                                        uint32_t* __restrict__ crc_rec, uint32_t* __restrict__ crc_tail,
                                                        BasesArg<TB> bases) {
     static_assert(NT == 1 || NT == 2, "cache policy 1 or 2");
-    static_assert(ST >= 0 && ST <= MT, "store policy 0, 1, or 2..MT: the last ST - 1 rows plain");
+    static_assert(ST >= kStoreWriteThrough && ST <= MT, "store policy -1, 0, 1, or 2..MT: the last ST - 1 rows plain");
+    static_assert(WMAX == 0 || WMAX >= WPS, "the occupancy cap is at least the floor");
     constexpr int NSH = K + MT;            // CRC: shards of the block (encode plans)
     constexpr int NSL = (NSH + 3) / 4;     // CRC: rows each lane keeps (r = q mod 4)
     __shared__ u32x4 s_tbl[K * kColDwords / 4];

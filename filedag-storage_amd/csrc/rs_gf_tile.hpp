@@ -148,8 +148,8 @@ __device__ __forceinline__ void gf_tile_columns(const u32x4* s_tbl, u32x4 (&v)[P
 
 // The output rows' chunk ch (< cpb) on an aligned layout: row j at ob + out_off[j].  A whole chunk
 // is stored under the store policy ST (store_policy, rs_plan.hpp: 0 plain, 1 nontemporal, n >= 2
-// nontemporal but the last n - 1 rows plain); the row's last, partial chunk (1..15 bytes) is
-// stored as whole dwords, then bytes, so no byte at or past S is ever written.
+// nontemporal but the last n - 1 rows plain, -1 write-through); the row's last, partial chunk
+// (1..15 bytes) is stored as whole dwords, then bytes, so no byte at or past S is ever written.
 template <int ST, int MT>
 __device__ __forceinline__ void store_rows_aligned(uint8_t* ob, const uint64_t (&out_off)[MT], uint32_t ch,
                                                    uint32_t S, const uint32_t (&acc)[MT][4]) {
@@ -158,7 +158,12 @@ __device__ __forceinline__ void store_rows_aligned(uint8_t* ob, const uint64_t (
 #pragma unroll
         for (int j = 0; j < MT; j++) {
             const u32x4 o = u32x4{acc[j][0], acc[j][1], acc[j][2], acc[j][3]};
-            if constexpr (ST == 1)
+            if constexpr (ST == kStoreWriteThrough)
+                // buffer_store_dwordx4 sc0 sc1 (cache policy 17) through a raw descriptor of the
+                // row's S bytes (gfx9 word 3: 32-bit data format), the chunk at byte boff
+                __builtin_amdgcn_raw_buffer_store_b128(
+                    o, __builtin_amdgcn_make_buffer_rsrc(ob + out_off[j], 0, int(S), 0x00020000), int(boff), 0, 17);
+            else if constexpr (ST == 1)
                 __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(ob + out_off[j]) + ch);
             else if (ST >= 2 && j + (ST - 1) < MT)  // a constant once the row loop is unrolled
                 __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(ob + out_off[j]) + ch);

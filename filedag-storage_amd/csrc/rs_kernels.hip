@@ -92,10 +92,11 @@ template <int K, int MT>
 static void fill_km(FastKernelTable& t) {
     constexpr int NT = auto_nt(K, MT);
     t.fn[K][MT] = reinterpret_cast<void*>(&rs_fast_kernel<K, MT, NT>);
-    // the rows of the grouped order store by the shape's own policy (store_policy, rs_plan.hpp)
-    if constexpr (store_policy_shape(K, MT, NT))
-        t.fn_sp[K][MT] = reinterpret_cast<void*>(
-            &rs_fast_kernel<K, MT, NT, kMinWavesPerSimd, false, false, false, store_policy(K, MT, NT)>);
+    // the rows of the grouped order run the shape's own kernel where it has one (store_policy,
+    // waves_cap, rs_plan.hpp)
+    if constexpr (grouped_kernel_shape(K, MT, NT))
+        t.fn_sp[K][MT] = reinterpret_cast<void*>(&rs_fast_kernel<K, MT, NT, kMinWavesPerSimd, false, false, false,
+                                                                 store_policy(K, MT, NT), waves_cap(K, MT)>);
     t.ua[K][MT] = reinterpret_cast<void*>(&rs_fast_kernel<K, MT, ua_nt(K, MT), kMinWavesPerSimd, true>);
     t.crc[K][MT] = reinterpret_cast<void*>(&rs_fast_kernel<K, MT, NT, kMinWavesPerSimd, false, true>);
     t.ua_crc[K][MT] = reinterpret_cast<void*>(&rs_fast_kernel<K, MT, NT, kMinWavesPerSimd, true, true>);

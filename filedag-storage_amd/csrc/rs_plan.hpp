@@ -11,7 +11,10 @@ constexpr int kFastWG = kWG;    // ... of the coding and verify kernels (one til
 constexpr int kMaxK = 256;      // k + m <= 256 (erasure.go:22)
 constexpr int kMaxMT = 4;       // outputs per launch tile
 constexpr int kColDwords = 20;  // per input column: 5 table fields x 4 outputs
-constexpr int kMinWavesPerSimd = 4;  // caps the fast kernels at 128 VGPRs (16 waves/CU)
+// The fast kernels' register budget: at least this many waves fit a SIMD (128 VGPRs).  A floor, not
+// a cap: a kernel that needs fewer registers runs at more waves (up to 8; DESIGN.md §4.1 lists the
+// aligned kernels) unless its shape has a cap of its own (waves_cap).
+constexpr int kMinWavesPerSimd = 4;
 // unaligned-window tiles: dword-aligned loads funnel-shifted for read-heavy tiles (1, the
 // default), for every UA tile (2), or byte-aligned 16-byte loads (0)
 #ifndef RSMI_UA_DWORD_LOADS
@@ -71,19 +74,32 @@ inline TileGroupShare tile_group_share(int K, int MT, uint32_t S) {
 // rsmi_core.cpp), which keeps naming the loads and the launch label:
 //   0  plain stores            1  nontemporal stores
 //   n >= 2  nontemporal stores, but the last n - 1 output rows plain
-// Measured under the grouped order on the two shapes that take it (profiles/store_path/ab.txt,
-// DESIGN.md §4.1): the RS(10,4) encode with its last parity row stored plain is 3.9 % faster than
-// with all four nontemporal (all plain -4.6 %, two plain rows slow the launch that follows); the
-// one-row reconstruct keeps its plain stores (nontemporal -5.8 %).  Every other shape, and longer
-// rows of these, keep what the cache policy says and the kernel they had (FastKernelTable::fn).
+//   -1  write-through stores (sc0 sc1: the line leaves the L2 with the store)
+// Measured under the grouped order on the two shapes that take it: the RS(10,4)
+// encode with its last parity row stored plain is 3.9 % faster than with all four nontemporal (all
+// plain -4.6 %, two plain rows slow the launch that follows; profiles/store_path/ab.txt); the
+// one-row reconstruct stores its row write-through, which takes 9 us off its 193 (nontemporal
+// -5.8 %; write-through for the last 512 / 1024 / 2048 / 3072 workgroups of each XCD's range of
+// 3328 gains the less the shorter the tail, and the encode's plain row written through gains
+// nothing; profiles/rec_inflight/ab.txt).  Every other shape, and longer rows of these, keep what
+// the cache policy says and the kernel they had (FastKernelTable::fn).
+constexpr int kStoreWriteThrough = -1;
 constexpr int store_policy(int K, int MT, int NT) {
     if (K == 10 && MT == 4) return 2;
+    if (K == 10 && MT == 1) return kStoreWriteThrough;
     return NT == 1 ? 1 : 0;
 }
-// a shape whose policy on those rows differs from its cache policy's has a kernel of its own for
-// them (FastKernelTable::fn_sp)
-constexpr bool store_policy_shape(int K, int MT, int NT) {
-    return tile_group_shape(K, MT) && store_policy(K, MT, NT) != (NT == 1 ? 1 : 0);
+// The most waves per SIMD that kernel runs at on those rows (0: whatever its registers allow,
+// kMinWavesPerSimd being the floor).  The one-row reconstruct needs 64 VGPRs, which alone would
+// put 8 waves on a SIMD, each with all 10 rows in flight: 320 KiB requested per CU.  Capped at 4
+// (160 KiB) the headline step gains 0.7 % (caps 6 / 5 / 3 / 2: 0.0 / +0.4 / +0.5 / -2.9 %; 8 or
+// 6 rows in flight instead of 10 lose 0.3-0.6 % uncapped and 0.3-0.5 % under the cap with a
+// write-through tail; profiles/rec_inflight/ab.txt).
+constexpr int waves_cap(int K, int MT) { return K == 10 && MT == 1 ? 4 : 0; }
+// a shape whose kernel on those rows differs from its cache policy's has one more instantiation
+// for them (FastKernelTable::fn_sp)
+constexpr bool grouped_kernel_shape(int K, int MT, int NT) {
+    return tile_group_shape(K, MT) && (store_policy(K, MT, NT) != (NT == 1 ? 1 : 0) || waves_cap(K, MT) != 0);
 }
 // head of a coding launch (launch_plan) of grid workgroups.  Unaligned-window layouts (ua): the
 // whole grid when it is a multiple of 8, else none (neighbouring tiles share cache lines there,
@@ -132,7 +148,7 @@ using BasesArg = std::conditional_t<TB, BlockBases, NoBases>;
 // of every row fused in (encode plans).
 struct FastKernelTable {
     void* fn[17][kMaxMT + 1];
-    void* fn_sp[17][kMaxMT + 1];  // aligned rows up to kGroupedRowMax of a store_policy_shape (null: fn)
+    void* fn_sp[17][kMaxMT + 1];  // aligned rows up to kGroupedRowMax of a grouped_kernel_shape (null: fn)
     void* ua[17][kMaxMT + 1];
     void* crc[17][kMaxMT + 1];
     void* ua_crc[17][kMaxMT + 1];

@@ -225,7 +225,9 @@ int auto_cache_policy(int K, int MT) { return K >= 4 * MT ? 2 : 1; }
 // The other per-shape choices of a launch are in rs_plan.hpp (there so that the kernels and the
 // host test share them): its tile order across XCDs, tile_group_share / launch_head, and, on the
 // rows that order takes, how the output rows are stored, store_policy, re-measured under that order
-// (RS(10,4) encode: the last parity row plain, +3.9 %; profiles/store_path/ab.txt).
+// (RS(10,4) encode: the last parity row plain, +3.9 %; profiles/store_path/ab.txt), and the most
+// waves a SIMD holds, waves_cap (RS(10,4) one-row reconstruct: its row written through, at most 4
+// waves; profiles/rec_inflight/ab.txt).
 
 uintptr_t table_alignment(const BlockBases* tb, uint64_t nblocks) {
     uintptr_t a = 0;
@@ -262,9 +264,10 @@ int launch_plan(rsmi_ctx* c, const Plan& plan, const uint8_t* in, uint64_t in_rs
             else if (fuse) fn = ua ? fast_kernels().ua_crc[t.K][t.MT] : fast_kernels().crc[t.K][t.MT];
             else if (aligned) fn = fast_kernels().fn[t.K][t.MT];
             else if (ua) fn = fast_kernels().ua[t.K][t.MT];
-            // the third per-shape choice, how the output rows are stored (store_policy,
-            // rs_plan.hpp): the plain aligned launch of a row the grouped order takes runs the
-            // shape's own kernel where it has one; the label stays the cache policy's
+            // the other per-shape choices, how the output rows are stored and how many waves a
+            // SIMD holds (store_policy, waves_cap, rs_plan.hpp): the plain aligned launch of a row
+            // the grouped order takes runs the shape's own kernel where it has one; the label
+            // stays the cache policy's
             if (aligned && !tb && !fuse && S <= kGroupedRowMax && fast_kernels().fn_sp[t.K][t.MT])
                 fn = fast_kernels().fn_sp[t.K][t.MT];
         }

@@ -23,7 +23,7 @@ def main():
     first = bench["config"]["settle"]["steps"] + bench["warmup"] + 1
     per = {}
     for r in rows:
-        m = re.search(r"rs_fast_kernel<(\d+), (\d+), (\d+), (\d+), (true|false), (true|false)(?:, (true|false))?(?:, \d+)?>", r["Kernel_Name"])
+        m = re.search(r"rs_fast_kernel<(\d+), (\d+), (\d+), (\d+), (true|false), (true|false)(?:, (true|false))?(?:, -?\d+)*>", r["Kernel_Name"])
         if not m:
             continue
         key = f"rs_fast_kernel<K={m.group(1)},MT={m.group(2)},NT={m.group(3)}>" + (",UA" if m.group(5) == "true" else "") + (
