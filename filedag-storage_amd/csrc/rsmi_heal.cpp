@@ -23,27 +23,23 @@ int launch_heal(rsmi_ctx* c, const Plan& plan, uint8_t* data, uint64_t data_rs, 
                 uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks, int32_t* culprit, uint32_t* bad,
                 hipStream_t stream) {
     if (nblocks == 0 || S == 0) return RSMI_OK;
-    bool fused = false;
+    StripeLayout fused = StripeLayout::kNeither;
     int rc = launch_locate(c, plan, data, data_rs, data_bs, parity, parity_rs, parity_bs, S, nblocks, culprit, bad,
                            stream, &fused);
     if (rc) return rc;
     // every shard explains any damage: nothing is ever named, the launches were Verify's
     if (c->m == 1) return RSMI_OK;
-    if (fused) {
-        // launch_verify's alignment test: rs_locate_kernel ran, so the layout is one of the two
-        const bool aligned = reinterpret_cast<uintptr_t>(data) % 16 == 0 &&
-                             reinterpret_cast<uintptr_t>(parity) % 16 == 0 && data_rs % 16 == 0 && data_bs % 16 == 0 &&
-                             parity_rs % 16 == 0 && parity_bs % 16 == 0 && data_rs >= round_up(S, 16) &&
-                             parity_rs >= round_up(S, 16);
+    if (fused != StripeLayout::kNeither) {
+        // the heal kernel of the layout rs_locate_kernel ran on
+        const bool aligned = fused == StripeLayout::kAligned;
         const DevTile& t = plan.tiles[0];
         void* fn = (aligned ? heal_kernels().fn : heal_kernels().ua)[t.K][t.MT];
         if (!fn) return RSMI_ERR_DEVICE;  // a locate kernel without its heal kernel: a build error
         std::shared_ptr<Plan> rp;
         if ((rc = ratio_plan(c, rp))) return rc;
         // rs_heal_kernel takes rs_locate_kernel's arguments, the verdicts in the candidates' place
-        rc = launch_stripe_tiles(c, fn, t, data, data_rs, data_bs, parity, parity_rs, parity_bs, S, nblocks,
-                                 reinterpret_cast<uint32_t*>(culprit), rp->tiles[0].dev,
-                                 reinterpret_cast<uint32_t*>(culprit), stream);
+        rc = launch_stripe_tiles(c, fn, t, data, data_rs, data_bs, parity, parity_rs, parity_bs, S, nblocks, nullptr,
+                                 rp->tiles[0].dev, culprit, stream);
         if (rc) return rc;
         char buf[96];
         std::snprintf(buf, sizeof buf, "rs_heal_kernel<K=%d,MT=%d>%s", t.K, t.MT, aligned ? "" : ",UA");
@@ -54,28 +50,22 @@ int launch_heal(rsmi_ctx* c, const Plan& plan, uint8_t* data, uint64_t data_rs, 
     // encoded again, chunk by chunk, and each chunk healed before the next one's encode.  A
     // healed data row differs from the stored one only in blocks of earlier chunks.
     if ((rc = ensure_locate_tables(c))) return rc;
-    const uint64_t k = uint64_t(c->k), m = uint64_t(c->m);
-    const uint64_t Sp = round_up(S, 16);
-    const uint64_t chunk = std::max<uint64_t>(1, (uint64_t(64) << 20) / (m * Sp));
-    rsmi_ctx::VerifyScratch& vs = stream_scratch(c->verify_scratch, stream);
-    if ((rc = reserve_on(vs.p, vs.cap, std::min(chunk, nblocks) * m * Sp, stream))) return rc;
-    for (uint64_t b0 = 0; b0 < nblocks; b0 += chunk) {
-        uint64_t nb = std::min(chunk, nblocks - b0);
-        rc = launch_plan(c, plan, data + b0 * data_bs, data_rs, data_bs, vs.p, Sp, m * Sp, S, nb, stream);
-        if (rc) return rc;
-        const uint8_t* enc = vs.p;
-        uint8_t* datab = data + b0 * data_bs;
-        uint8_t* parb = parity + b0 * parity_bs;
-        uint64_t enc_bs = m * Sp, enc_rs = Sp, S64 = S;
-        uint32_t k32 = uint32_t(k), m32 = uint32_t(m);
-        const int32_t* verdict = culprit + b0;
-        const uint8_t* tbl = c->d_locate_tbl;
-        const uint32_t gx = uint32_t(std::min<uint64_t>((S + kWG - 1) / kWG, 4096));
-        const uint32_t gy = uint32_t(std::min<uint64_t>(nb, 65535));
-        void* args[] = {&enc,  &enc_rs,    &enc_bs,    &datab, &data_rs, &data_bs, &parb, &parity_rs,
-                        &parity_bs, &S64, &k32,   &m32,     &nb,      &verdict, &tbl};
-        HIP_TRY(hipLaunchKernel(heal_rows_kernel(), dim3(gx, gy), dim3(kWG), args, 0, stream));
-    }
+    rc = encode_into_scratch(
+        c, plan, data, data_rs, data_bs, S, nblocks, stream,
+        [&](uint64_t b0, uint64_t nb, const uint8_t* enc, uint64_t enc_rs, uint64_t enc_bs) -> int {
+            uint8_t* datab = data + b0 * data_bs;
+            uint8_t* parb = parity + b0 * parity_bs;
+            uint32_t k32 = uint32_t(c->k), m32 = uint32_t(c->m);
+            const int32_t* verdict = culprit + b0;
+            const uint8_t* tbl = c->d_locate_tbl;
+            const uint32_t gx = uint32_t(std::min<uint64_t>((S + kWG - 1) / kWG, 4096));
+            const uint32_t gy = uint32_t(std::min<uint64_t>(nb, 65535));
+            void* args[] = {&enc,  &enc_rs,    &enc_bs,    &datab, &data_rs, &data_bs, &parb, &parity_rs,
+                            &parity_bs, &S, &k32,   &m32,     &nb,      &verdict, &tbl};
+            HIP_TRY(hipLaunchKernel(heal_rows_kernel(), dim3(gx, gy), dim3(kWG), args, 0, stream));
+            return RSMI_OK;
+        });
+    if (rc) return rc;
     set_last_kernel(c, "rs_heal_rows_kernel");
     return hip_status(hipGetLastError());
 }
@@ -83,40 +73,22 @@ int launch_heal(rsmi_ctx* c, const Plan& plan, uint8_t* data, uint64_t data_rs, 
 // Host-memory heal on Verify's host paths: locate_host_impl's buffers, and the write-back leg.
 int heal_host_impl(rsmi_ctx* c, uint8_t* data, size_t data_block_stride, uint8_t* parity, size_t parity_block_stride,
                    size_t S, size_t nblocks, int32_t* culprit_out, uint32_t* bad_out) {
-    if (!c || !data || !parity || !culprit_out) return RSMI_ERR_INVALID_ARG;
-    if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
-    if (data_block_stride < size_t(c->k) * S || parity_block_stride < size_t(c->m) * S) return RSMI_ERR_INVALID_ARG;
+    if (int rc = check_stripe_host_args(c, data, data_block_stride, parity, parity_block_stride, S, culprit_out))
+        return rc;
     if (nblocks == 0) return RSMI_OK;
-    const size_t k = size_t(c->k), m = size_t(c->m), flag_bytes = nblocks * m * sizeof(uint32_t);
-    const size_t verdict_bytes = nblocks * sizeof(int32_t);
-    uint32_t* d_bad = nullptr;
-    int32_t* d_culprit = nullptr;
+    const size_t k = size_t(c->k), m = size_t(c->m);
     // where the caller keeps row x of block b
     auto home = [&](size_t b, size_t x) -> uint8_t* {
         return x < k ? data + b * data_block_stride + x * S : parity + b * parity_block_stride + (x - k) * S;
     };
+    StripeResults r;
     StripeCheck chk;
-    chk.prepare = [&]() -> int {
-        int rc = reserve(c->d_vbad, c->vbad_cap, flag_bytes + verdict_bytes);
-        d_bad = reinterpret_cast<uint32_t*>(c->d_vbad);
-        d_culprit = reinterpret_cast<int32_t*>(d_bad + nblocks * m);
-        return rc;
-    };
+    stripe_results(c, nblocks, culprit_out, bad_out, r, chk);
     chk.launch = [&](const Plan& plan, const uint8_t* d, uint64_t d_rs, uint64_t d_bs, const uint8_t* p, uint64_t p_rs,
                      uint64_t p_bs, uint64_t nb, uint64_t b0, hipStream_t st) -> int {
         // the rows are the caller's own (in place) or the call's staging: writable either way
         return launch_heal(c, plan, const_cast<uint8_t*>(d), d_rs, d_bs, const_cast<uint8_t*>(p), p_rs, p_bs, S, nb,
-                           d_culprit + b0, d_bad + b0 * m, st);
-    };
-    chk.fetch = [&](hipStream_t st) -> int {
-        if (st) {
-            HIP_TRY(hipMemcpyAsync(culprit_out, d_culprit, verdict_bytes, hipMemcpyDeviceToHost, st));
-            if (bad_out) HIP_TRY(hipMemcpyAsync(bad_out, d_bad, flag_bytes, hipMemcpyDeviceToHost, st));
-        } else {
-            HIP_TRY(hipMemcpy(culprit_out, d_culprit, verdict_bytes, hipMemcpyDeviceToHost));
-            if (bad_out) HIP_TRY(hipMemcpy(bad_out, d_bad, flag_bytes, hipMemcpyDeviceToHost));
-        }
-        return RSMI_OK;
+                           r.d_culprit + b0, r.d_bad + b0 * m, st);
     };
     // the small staged call: the verdicts are in culprit_out, the healed rows in the staging
     chk.small_done = [&](const uint8_t* sd, const uint8_t* sp) -> int {
@@ -132,7 +104,7 @@ int heal_host_impl(rsmi_ctx* c, uint8_t* data, size_t data_block_stride, uint8_t
     // the upload pipeline: a chunk's verdicts, then its healed rows from the device pitch to the
     // caller's, before the staging slot is filled again
     chk.chunk_done = [&](Staging& st, uint64_t b0, uint64_t nb, size_t Sp) -> int {
-        HIP_TRY(hipMemcpyAsync(culprit_out + b0, d_culprit + b0, nb * sizeof(int32_t), hipMemcpyDeviceToHost,
+        HIP_TRY(hipMemcpyAsync(culprit_out + b0, r.d_culprit + b0, nb * sizeof(int32_t), hipMemcpyDeviceToHost,
                                st.stream));
         HIP_TRY(hipStreamSynchronize(st.stream));
         for (uint64_t b = 0; b < nb; b++) {
@@ -158,17 +130,12 @@ extern "C" {
 int rsmi_heal_batch_dev(rsmi_ctx* c, uint8_t* d_data, size_t data_shard_stride, size_t data_block_stride,
                         uint8_t* d_parity, size_t parity_shard_stride, size_t parity_block_stride, size_t S,
                         size_t nblocks, int32_t* d_culprit_out, uint32_t* d_bad_out, void* stream) try {
-    if (!c || !d_data || !d_parity || !d_culprit_out) return RSMI_ERR_INVALID_ARG;
-    if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
-    if (data_shard_stride < S || parity_shard_stride < S) return RSMI_ERR_INVALID_ARG;
+    int rc = check_stripe_dev_args(c, d_data, data_shard_stride, d_parity, parity_shard_stride, S, d_culprit_out);
+    if (rc) return rc;
     if (nblocks == 0) return RSMI_OK;
     std::shared_ptr<Plan> plan;
-    std::lock_guard<std::mutex> g(c->mu);
-    int rc = ensure_device(c);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    rc = encode_plan(c, plan);
-    if (rc) return rc;
+    std::unique_lock<std::mutex> lock;
+    if ((rc = begin_stripe_dev_call(c, lock, plan))) return rc;
     return launch_heal(c, *plan, d_data, data_shard_stride, data_block_stride, d_parity, parity_shard_stride,
                        parity_block_stride, S, nblocks, d_culprit_out, d_bad_out, static_cast<hipStream_t>(stream));
 } catch (...) {

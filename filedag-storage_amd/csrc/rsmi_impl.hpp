@@ -3,7 +3,9 @@
 //   rsmi_host.cpp      host-memory calls: zero-copy single kernel, copy-engine pipeline
 //   rsmi_crc.cpp       datanode CRC-16 on the GPU (separate pass and fused into the encode)
 //   rsmi_coalesce.cpp  group commit of concurrent single-block calls
-//   rsmi_verify.cpp    Encoder.Verify: stored parity checked against the data rows
+//   rsmi_verify.cpp    Encoder.Verify: stored parity checked against the data rows; what the three
+//                      stripe checks share: the layout test, the tile launch, the scratch-encode
+//                      fallback, the host paths, the entry points' checks and prologue
 //   rsmi_locate.cpp    rsmi_locate: the shard that breaks a stripe, from Verify's syndromes
 //   rsmi_heal.cpp      rsmi_heal: locate, then the named shard rewritten on the same stream
 // No CPU compute path anywhere: every byte of parity, reconstructed data or CRC and every verify
@@ -268,31 +270,51 @@ int reconstruct_small(rsmi_ctx* c, const Plan& plan, uint8_t* shards, size_t bs,
 int reconstruct_host_impl(rsmi_ctx* c, uint8_t* shards, size_t block_stride, size_t S, size_t nblocks,
                                  const uint8_t* present, const uint8_t* want, uint32_t* raw16 = nullptr,
                           uint32_t* raw32 = nullptr);
+// The layout of a stripe's rows (rsmi_verify.cpp), which picks the tile kernels' form: 16-byte
+// aligned, unaligned windows (UA), or neither (the scratch-encode fallback).
+enum class StripeLayout { kAligned, kUA, kNeither };
+StripeLayout stripe_layout(const uint8_t* data, uint64_t data_rs, uint64_t data_bs, const uint8_t* parity,
+                           uint64_t parity_rs, uint64_t parity_bs, uint64_t S);
 // Encoder.Verify of nblocks blocks (rsmi_verify.cpp; caller holds ctx->mu): bad[b*m + j], device
 // memory, zeroed here on the stream, then non-zero where stored parity row j of block b differs
 // from the encode of the block's data rows.  Stream-ordered, no synchronisation.
 // loc (rsmi_locate.cpp): where the shape has an rs_locate_kernel, that kernel runs in the place of
 // rs_verify_kernel and also ANDs the shards that explain each dirty tile into cand[b] (one word
-// per block, all-ones on the stream before the call; rplan: the ratio matrix's tables); fused
-// says whether it did.
+// per block, all-ones on the stream before the call; rplan: the ratio matrix's tables); fused is
+// the layout it ran on, kNeither when it did not run.
 struct LocateFuse {
     const RsPlanDev* rplan = nullptr;
     uint32_t* cand = nullptr;
-    bool fused = false;
+    StripeLayout fused = StripeLayout::kNeither;
 };
 int launch_verify(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
                   const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks,
                   uint32_t* bad, hipStream_t stream, LocateFuse* loc = nullptr);
-// One tile's rs_verify_kernel fn over nblocks blocks, or (rplan and cand given) its
-// rs_locate_kernel: one tile per wave unless waves_per_cu caps the grid, in launches whose tile
-// count fits 32 bits.
+// One tile's rs_verify_kernel fn over nblocks blocks, or (rplan given) its rs_locate_kernel or
+// rs_heal_kernel: one tile per wave unless waves_per_cu caps the grid, in launches whose tile
+// count fits 32 bits.  words: the last kernel argument, one 32-bit word per block: the candidates
+// of rs_locate_kernel, the verdicts of rs_heal_kernel (which takes no bad).
 int launch_stripe_tiles(rsmi_ctx* c, void* fn, const DevTile& t, const uint8_t* data, uint64_t data_rs,
                         uint64_t data_bs, const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S,
-                        uint64_t nblocks, uint32_t* bad, const RsPlanDev* rplan, uint32_t* cand, hipStream_t stream);
+                        uint64_t nblocks, uint32_t* bad, const RsPlanDev* rplan, void* words, hipStream_t stream);
 // The stream's entry of a per-stream scratch map (caller holds ctx->mu): verify_scratch, the
 // fallback's encoded rows; locate_scratch.  Past 32 streams the device is drained once and every
 // stream's scratch freed.
 rsmi_ctx::VerifyScratch& stream_scratch(std::map<hipStream_t, rsmi_ctx::VerifyScratch>& map, hipStream_t st);
+// The fallback of the shapes without a tile kernel: the encode of the data rows into the stream's
+// verify_scratch (16-byte-aligned rows), at most 64 MiB of scratch rows at a time, and per chunk
+// of nb blocks from block b0 the caller's byte-granular launch, before the next encode reuses them.
+using ScratchRowsFn = std::function<int(uint64_t b0, uint64_t nb, const uint8_t* enc, uint64_t enc_rs, uint64_t enc_bs)>;
+int encode_into_scratch(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
+                        uint64_t S, uint64_t nblocks, hipStream_t stream, const ScratchRowsFn& fn);
+// The argument checks of the *_batch_dev entries and of the host impls (out: the output that must
+// be given), and the device entries' prologue: ctx->mu taken into lock, the device bound, the
+// encode plan (declared before lock by the caller, so it outlives the lock).
+int check_stripe_dev_args(const rsmi_ctx* c, const void* d_data, size_t data_shard_stride, const void* d_parity,
+                          size_t parity_shard_stride, size_t S, const void* out);
+int check_stripe_host_args(const rsmi_ctx* c, const void* data, size_t data_block_stride, const void* parity,
+                           size_t parity_block_stride, size_t S, const void* out);
+int begin_stripe_dev_call(rsmi_ctx* c, std::unique_lock<std::mutex>& lock, std::shared_ptr<Plan>& plan);
 // What a host-memory call runs over stored stripes (Encoder.Verify, rsmi_locate): verify_host_impl
 // stages or uploads the rows on one of rsmi_verify_batch_host's three paths and calls
 //   prepare()  once, under ctx->mu with the device bound: the call's device result buffers
@@ -316,12 +338,21 @@ struct StripeCheck {
 };
 int verify_host_impl(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
                      size_t parity_block_stride, size_t S, size_t nblocks, const StripeCheck& chk);
+// The device result buffer of a host call, in ctx->d_vbad: the flags of nblocks blocks, then (locate
+// and heal: culprit_out given) their verdicts.  stripe_results sets chk.prepare, which reserves it
+// and sets r, and chk.fetch, which copies out what the caller takes.  r must outlive chk.
+struct StripeResults {
+    uint32_t* d_bad = nullptr;
+    int32_t* d_culprit = nullptr;
+};
+void stripe_results(rsmi_ctx* c, size_t nblocks, int32_t* culprit_out, uint32_t* bad_out, StripeResults& r,
+                    StripeCheck& chk);
 // rsmi_locate of nblocks blocks (rsmi_locate.cpp; caller holds ctx->mu): verdicts culprit[b] and,
-// when bad is given, Verify's flags, device memory, stream-ordered.  fused: whether rs_locate_kernel
-// ran (false: m = 1, or the encode into scratch and rs_locate_rows_kernel).
+// when bad is given, Verify's flags, device memory, stream-ordered.  fused: the layout
+// rs_locate_kernel ran on (kNeither: m = 1, or the encode into scratch and rs_locate_rows_kernel).
 int launch_locate(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
                   const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks,
-                  int32_t* culprit, uint32_t* bad, hipStream_t stream, bool* fused = nullptr);
+                  int32_t* culprit, uint32_t* bad, hipStream_t stream, StripeLayout* fused = nullptr);
 // the ratio matrix's plan "L" (output slot 0: inv(M[k][c])) and the byte-granular kernels' tables
 // (ctx->d_locate_tbl: log | exp | R | inv(M[k][c])), both built on first use
 int ratio_plan(rsmi_ctx* c, std::shared_ptr<Plan>& out);

@@ -68,11 +68,11 @@ int ensure_locate_tables(rsmi_ctx* c) {
 // Locate of nblocks blocks (caller holds ctx->mu, the device is bound): culprit[b] and, when bad
 // is given, Verify's flags bad[b*m + j], both device memory.  Stream-ordered; the candidate words
 // (and the flags, when the caller takes none) live in the stream's scratch.  fused (rsmi_heal.cpp):
-// whether rs_locate_kernel ran (false: m = 1 or the fallback).
+// the layout rs_locate_kernel ran on (kNeither: m = 1 or the fallback).
 int launch_locate(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
                   const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks,
-                  int32_t* culprit, uint32_t* bad, hipStream_t stream, bool* fused) {
-    if (fused) *fused = false;
+                  int32_t* culprit, uint32_t* bad, hipStream_t stream, StripeLayout* fused) {
+    if (fused) *fused = StripeLayout::kNeither;
     if (nblocks == 0 || S == 0) return RSMI_OK;
     const uint64_t k = uint64_t(c->k), m = uint64_t(c->m);
     uint32_t n32 = uint32_t(c->n), m32 = uint32_t(m), words = (n32 + 31u) / 32u;
@@ -103,33 +103,29 @@ int launch_locate(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t d
                                 rp ? &loc : nullptr)))
             return rc;
         if (fused) *fused = loc.fused;
-        if (!loc.fused) {
+        if (loc.fused == StripeLayout::kNeither) {
             // m > 4, K > 16 or not instantiated, unaligned rows shorter than 16 bytes: Verify's
             // launch gave the flags; now the parity rows encoded into scratch (as Verify's own
-            // fallback does, at most 64 MiB at a time) and the byte-granular kernel over the
-            // blocks whose flags are set.  The correctness path of rare shapes.
+            // fallback does) and the byte-granular kernel over the blocks whose flags are set.
+            // The correctness path of rare shapes.
             if ((rc = ensure_locate_tables(c))) return rc;
-            const uint64_t Sp = round_up(S, 16);
-            const uint64_t chunk = std::max<uint64_t>(1, (uint64_t(64) << 20) / (m * Sp));
-            rsmi_ctx::VerifyScratch& vs = stream_scratch(c->verify_scratch, stream);
-            if ((rc = reserve_on(vs.p, vs.cap, std::min(chunk, nblocks) * m * Sp, stream))) return rc;
-            for (uint64_t b0 = 0; b0 < nblocks; b0 += chunk) {
-                uint64_t nb = std::min(chunk, nblocks - b0);
-                rc = launch_plan(c, plan, data + b0 * data_bs, data_rs, data_bs, vs.p, Sp, m * Sp, S, nb, stream);
-                if (rc) return rc;
-                const uint8_t* enc = vs.p;
-                const uint8_t* parb = parity + b0 * parity_bs;
-                uint64_t enc_bs = m * Sp, enc_rs = Sp, S64 = S;
-                uint32_t k32 = uint32_t(k);
-                const uint32_t* badb = bad + b0 * m;
-                const uint8_t* tbl = c->d_locate_tbl;
-                uint32_t* candb = cand + b0 * words;
-                const uint32_t gx = uint32_t(std::min<uint64_t>((S + kWG - 1) / kWG, 4096));
-                const uint32_t gy = uint32_t(std::min<uint64_t>(nb, 65535));
-                void* args[] = {&enc, &enc_rs, &enc_bs, &parb, &parity_rs, &parity_bs, &S64,
-                                &k32, &m32,    &nb,     &badb, &tbl,       &candb};
-                HIP_TRY(hipLaunchKernel(locate_rows_kernel(), dim3(gx, gy), dim3(kWG), args, size_t(m * k), stream));
-            }
+            rc = encode_into_scratch(
+                c, plan, data, data_rs, data_bs, S, nblocks, stream,
+                [&](uint64_t b0, uint64_t nb, const uint8_t* enc, uint64_t enc_rs, uint64_t enc_bs) -> int {
+                    const uint8_t* parb = parity + b0 * parity_bs;
+                    uint32_t k32 = uint32_t(k);
+                    const uint32_t* badb = bad + b0 * m;
+                    const uint8_t* tbl = c->d_locate_tbl;
+                    uint32_t* candb = cand + b0 * words;
+                    const uint32_t gx = uint32_t(std::min<uint64_t>((S + kWG - 1) / kWG, 4096));
+                    const uint32_t gy = uint32_t(std::min<uint64_t>(nb, 65535));
+                    void* args[] = {&enc, &enc_rs, &enc_bs, &parb, &parity_rs, &parity_bs, &S,
+                                    &k32, &m32,    &nb,     &badb, &tbl,       &candb};
+                    HIP_TRY(hipLaunchKernel(locate_rows_kernel(), dim3(gx, gy), dim3(kWG), args, size_t(m * k),
+                                            stream));
+                    return RSMI_OK;
+                });
+            if (rc) return rc;
             set_last_kernel(c, "rs_locate_rows_kernel");
         }
     }
@@ -148,34 +144,16 @@ namespace {
 // context's device result buffer, flags first.
 int locate_host_impl(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
                      size_t parity_block_stride, size_t S, size_t nblocks, int32_t* culprit_out, uint32_t* bad_out) {
-    if (!c || !data || !parity || !culprit_out) return RSMI_ERR_INVALID_ARG;
-    if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
-    if (data_block_stride < size_t(c->k) * S || parity_block_stride < size_t(c->m) * S) return RSMI_ERR_INVALID_ARG;
-    if (nblocks == 0) return RSMI_OK;
-    const size_t m = size_t(c->m), flag_bytes = nblocks * m * sizeof(uint32_t);
-    const size_t verdict_bytes = nblocks * sizeof(int32_t);
-    uint32_t* d_bad = nullptr;
-    int32_t* d_culprit = nullptr;
-    StripeCheck chk;
-    chk.prepare = [&]() -> int {
-        int rc = reserve(c->d_vbad, c->vbad_cap, flag_bytes + verdict_bytes);
-        d_bad = reinterpret_cast<uint32_t*>(c->d_vbad);
-        d_culprit = reinterpret_cast<int32_t*>(d_bad + nblocks * m);
+    if (int rc = check_stripe_host_args(c, data, data_block_stride, parity, parity_block_stride, S, culprit_out))
         return rc;
-    };
+    if (nblocks == 0) return RSMI_OK;
+    const size_t m = size_t(c->m);
+    StripeResults r;
+    StripeCheck chk;
+    stripe_results(c, nblocks, culprit_out, bad_out, r, chk);
     chk.launch = [&](const Plan& plan, const uint8_t* d, uint64_t d_rs, uint64_t d_bs, const uint8_t* p, uint64_t p_rs,
                      uint64_t p_bs, uint64_t nb, uint64_t b0, hipStream_t st) -> int {
-        return launch_locate(c, plan, d, d_rs, d_bs, p, p_rs, p_bs, S, nb, d_culprit + b0, d_bad + b0 * m, st);
-    };
-    chk.fetch = [&](hipStream_t st) -> int {
-        if (st) {
-            HIP_TRY(hipMemcpyAsync(culprit_out, d_culprit, verdict_bytes, hipMemcpyDeviceToHost, st));
-            if (bad_out) HIP_TRY(hipMemcpyAsync(bad_out, d_bad, flag_bytes, hipMemcpyDeviceToHost, st));
-        } else {
-            HIP_TRY(hipMemcpy(culprit_out, d_culprit, verdict_bytes, hipMemcpyDeviceToHost));
-            if (bad_out) HIP_TRY(hipMemcpy(bad_out, d_bad, flag_bytes, hipMemcpyDeviceToHost));
-        }
-        return RSMI_OK;
+        return launch_locate(c, plan, d, d_rs, d_bs, p, p_rs, p_bs, S, nb, r.d_culprit + b0, r.d_bad + b0 * m, st);
     };
     return verify_host_impl(c, data, data_block_stride, parity, parity_block_stride, S, nblocks, chk);
 }
@@ -190,17 +168,12 @@ extern "C" {
 int rsmi_locate_batch_dev(rsmi_ctx* c, const uint8_t* d_data, size_t data_shard_stride, size_t data_block_stride,
                           const uint8_t* d_parity, size_t parity_shard_stride, size_t parity_block_stride, size_t S,
                           size_t nblocks, int32_t* d_culprit_out, uint32_t* d_bad_out, void* stream) try {
-    if (!c || !d_data || !d_parity || !d_culprit_out) return RSMI_ERR_INVALID_ARG;
-    if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
-    if (data_shard_stride < S || parity_shard_stride < S) return RSMI_ERR_INVALID_ARG;
+    int rc = check_stripe_dev_args(c, d_data, data_shard_stride, d_parity, parity_shard_stride, S, d_culprit_out);
+    if (rc) return rc;
     if (nblocks == 0) return RSMI_OK;
     std::shared_ptr<Plan> plan;
-    std::lock_guard<std::mutex> g(c->mu);
-    int rc = ensure_device(c);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    rc = encode_plan(c, plan);
-    if (rc) return rc;
+    std::unique_lock<std::mutex> lock;
+    if ((rc = begin_stripe_dev_call(c, lock, plan))) return rc;
     return launch_locate(c, *plan, d_data, data_shard_stride, data_block_stride, d_parity, parity_shard_stride,
                          parity_block_stride, S, nblocks, d_culprit_out, d_bad_out, static_cast<hipStream_t>(stream));
 } catch (...) {

@@ -4,7 +4,9 @@
 // rs_verify_kernel (rs_verify_kernels.hip) over the tiles of the cached encode plan, or, for
 // shapes it is not built for, the encode into scratch followed by rs_compare_rows_kernel.
 // rsmi_locate (rsmi_locate.cpp) shares the launch (launch_verify with a LocateFuse) and the host
-// paths (verify_host_impl with its own StripeCheck).
+// paths (verify_host_impl with its own StripeCheck).  What rsmi_locate and rsmi_heal share with
+// Verify beyond that lives here as well: stripe_layout, launch_stripe_tiles, encode_into_scratch,
+// stripe_results, the entry points' argument checks and begin_stripe_dev_call.
 
 #include "rsmi_impl.hpp"
 
@@ -30,7 +32,7 @@ rsmi_ctx::VerifyScratch& stream_scratch(std::map<hipStream_t, rsmi_ctx::VerifySc
 
 int launch_stripe_tiles(rsmi_ctx* c, void* fn, const DevTile& t, const uint8_t* data, uint64_t data_rs,
                         uint64_t data_bs, const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S,
-                        uint64_t nblocks, uint32_t* bad, const RsPlanDev* rplan, uint32_t* cand, hipStream_t stream) {
+                        uint64_t nblocks, uint32_t* bad, const RsPlanDev* rplan, void* words, hipStream_t stream) {
     const uint64_t m = uint64_t(c->m);
     const uint64_t cpb = (S + 15) / 16;
     const uint64_t tpb = (cpb + uint64_t(kWave) - 1) / uint64_t(kWave);
@@ -46,13 +48,41 @@ int launch_stripe_tiles(rsmi_ctx* c, void* fn, const DevTile& t, const uint8_t* 
         const RsPlanDev* pd = t.dev;
         const uint8_t* inb = data + b0 * data_bs;
         const uint8_t* parb = parity + b0 * parity_bs;
-        uint32_t* badb = bad + b0 * m;
-        uint32_t* candb = cand ? cand + b0 : nullptr;
-        // rs_locate_kernel's parameters are rs_verify_kernel's and these two more
+        uint32_t* badb = bad ? bad + b0 * m : nullptr;
+        void* wordsb = words ? static_cast<uint8_t*>(words) + b0 * sizeof(uint32_t) : nullptr;
+        // rs_locate_kernel's and rs_heal_kernel's parameters are rs_verify_kernel's and these two more
         void* args[] = {&pd,  &inb,   &parb,  &data_bs, &data_rs, &parity_bs, &parity_rs, &S32,
-                        &cpb32, &tpb32, &ntiles,  &badb,    &m32,       &rplan,     &candb};
+                        &cpb32, &tpb32, &ntiles,  &badb,    &m32,       &rplan,     &wordsb};
         const uint64_t wgs = std::min<uint64_t>((ntiles + wpg - 1) / wpg, uint64_t(wg_cap));
         HIP_TRY(hipLaunchKernel(fn, dim3(uint32_t(wgs)), dim3(uint32_t(wpg * kWave)), args, 0, stream));
+    }
+    return RSMI_OK;
+}
+
+// the alignment test of launch_plan, the stored parity rows in the place of the output rows
+StripeLayout stripe_layout(const uint8_t* data, uint64_t data_rs, uint64_t data_bs, const uint8_t* parity,
+                           uint64_t parity_rs, uint64_t parity_bs, uint64_t S) {
+    const bool aligned = reinterpret_cast<uintptr_t>(data) % 16 == 0 && reinterpret_cast<uintptr_t>(parity) % 16 == 0 &&
+                         data_rs % 16 == 0 && data_bs % 16 == 0 && parity_rs % 16 == 0 && parity_bs % 16 == 0 &&
+                         data_rs >= round_up(S, 16) && parity_rs >= round_up(S, 16) && S < (uint64_t(1) << 31);
+    const bool ua = !aligned && S >= 16 && S < (uint64_t(1) << 31) && data_rs >= S && parity_rs >= S;
+    return aligned ? StripeLayout::kAligned : ua ? StripeLayout::kUA : StripeLayout::kNeither;
+}
+
+int encode_into_scratch(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
+                        uint64_t S, uint64_t nblocks, hipStream_t stream, const ScratchRowsFn& fn) {
+    const uint64_t m = uint64_t(c->m);
+    const uint64_t Sp = round_up(S, 16);
+    const uint64_t chunk = std::max<uint64_t>(1, (uint64_t(64) << 20) / (m * Sp));
+    rsmi_ctx::VerifyScratch& vs = stream_scratch(c->verify_scratch, stream);
+    int rc = reserve_on(vs.p, vs.cap, std::min(chunk, nblocks) * m * Sp, stream);
+    if (rc) return rc;
+    for (uint64_t b0 = 0; b0 < nblocks; b0 += chunk) {
+        const uint64_t nb = std::min(chunk, nblocks - b0);
+        rc = launch_plan(c, plan, data + b0 * data_bs, data_rs, data_bs, vs.p, Sp, m * Sp, S, nb, stream);
+        if (rc) return rc;
+        const uint64_t enc_bs = m * Sp, enc_rs = Sp;
+        if ((rc = fn(b0, nb, vs.p, enc_rs, enc_bs))) return rc;
     }
     return RSMI_OK;
 }
@@ -60,15 +90,12 @@ int launch_stripe_tiles(rsmi_ctx* c, void* fn, const DevTile& t, const uint8_t* 
 int launch_verify(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
                   const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks,
                   uint32_t* bad, hipStream_t stream, LocateFuse* loc) {
-    if (loc) loc->fused = false;
+    if (loc) loc->fused = StripeLayout::kNeither;
     if (nblocks == 0 || S == 0) return RSMI_OK;
     const uint64_t m = uint64_t(c->m);
     HIP_TRY(hipMemsetAsync(bad, 0, nblocks * m * sizeof(uint32_t), stream));
-    // the alignment test of launch_plan, the stored parity rows in the place of the output rows
-    const bool aligned = reinterpret_cast<uintptr_t>(data) % 16 == 0 && reinterpret_cast<uintptr_t>(parity) % 16 == 0 &&
-                         data_rs % 16 == 0 && data_bs % 16 == 0 && parity_rs % 16 == 0 && parity_bs % 16 == 0 &&
-                         data_rs >= round_up(S, 16) && parity_rs >= round_up(S, 16) && S < (uint64_t(1) << 31);
-    const bool ua = !aligned && S >= 16 && S < (uint64_t(1) << 31) && data_rs >= S && parity_rs >= S;
+    const StripeLayout layout = stripe_layout(data, data_rs, data_bs, parity, parity_rs, parity_bs, S);
+    const bool aligned = layout == StripeLayout::kAligned, ua = layout == StripeLayout::kUA;
     bool fast = aligned || ua;
     for (const DevTile& t : plan.tiles)
         if (t.K > 16 || !(aligned ? verify_kernels().fn : verify_kernels().ua)[t.K][t.MT]) fast = false;
@@ -89,34 +116,27 @@ int launch_verify(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t d
                           ua ? ",UA" : "");
             label = buf;
         }
-        if (loc) loc->fused = lfn != nullptr;
+        if (loc && lfn) loc->fused = layout;
         set_last_kernel(c, label);
         return hip_status(hipGetLastError());
     }
     // Shapes without an rs_verify_kernel (K > 16 or not instantiated, unaligned rows shorter than
-    // 16 bytes): the parity rows are encoded into scratch (16-byte-aligned rows, so the coding
-    // launch is whatever the data rows' layout allows) and compared with the stored ones,
-    // at most 64 MiB of scratch rows at a time.  The correctness path of rare shapes.
-    const uint64_t Sp = round_up(S, 16);
-    const uint64_t chunk = std::max<uint64_t>(1, (uint64_t(64) << 20) / (m * Sp));
-    rsmi_ctx::VerifyScratch& vs = stream_scratch(c->verify_scratch, stream);
-    int rc = reserve_on(vs.p, vs.cap, std::min(chunk, nblocks) * m * Sp, stream);
+    // 16 bytes): the parity rows are encoded into scratch and compared with the stored ones.  The
+    // correctness path of rare shapes.
+    int rc = encode_into_scratch(
+        c, plan, data, data_rs, data_bs, S, nblocks, stream,
+        [&](uint64_t b0, uint64_t nb, const uint8_t* enc, uint64_t enc_rs, uint64_t enc_bs) -> int {
+            const uint8_t* parb = parity + b0 * parity_bs;
+            uint32_t m32 = uint32_t(m);
+            uint32_t* badb = bad + b0 * m;
+            const uint64_t groups = (S + 3) / 4;
+            const uint32_t gx = uint32_t(std::min<uint64_t>((groups + kWG - 1) / kWG, 4096));
+            const uint32_t gy = uint32_t(std::min<uint64_t>(nb, 65535));
+            void* args[] = {&enc, &enc_rs, &enc_bs, &parb, &parity_rs, &parity_bs, &S, &m32, &nb, &badb};
+            HIP_TRY(hipLaunchKernel(compare_rows_kernel(), dim3(gx, gy), dim3(kWG), args, 0, stream));
+            return RSMI_OK;
+        });
     if (rc) return rc;
-    for (uint64_t b0 = 0; b0 < nblocks; b0 += chunk) {
-        const uint64_t nb = std::min(chunk, nblocks - b0);
-        rc = launch_plan(c, plan, data + b0 * data_bs, data_rs, data_bs, vs.p, Sp, m * Sp, S, nb, stream);
-        if (rc) return rc;
-        const uint8_t* enc = vs.p;
-        const uint8_t* parb = parity + b0 * parity_bs;
-        uint64_t enc_bs = m * Sp, enc_rs = Sp, n = nb;
-        uint32_t m32 = uint32_t(m);
-        uint32_t* badb = bad + b0 * m;
-        const uint64_t groups = (S + 3) / 4;
-        const uint32_t gx = uint32_t(std::min<uint64_t>((groups + kWG - 1) / kWG, 4096));
-        const uint32_t gy = uint32_t(std::min<uint64_t>(nb, 65535));
-        void* args[] = {&enc, &enc_rs, &enc_bs, &parb, &parity_rs, &parity_bs, &S, &m32, &n, &badb};
-        HIP_TRY(hipLaunchKernel(compare_rows_kernel(), dim3(gx, gy), dim3(kWG), args, 0, stream));
-    }
     set_last_kernel(c, "rs_compare_rows_kernel");
     return hip_status(hipGetLastError());
 }
@@ -235,34 +255,68 @@ int verify_host_impl(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride,
     return chk.fetch(nullptr);
 }
 
-namespace {
-
-// Host-memory verify: the flags live in device memory on every path (no atomics aimed at host
-// memory); every host call synchronises before it returns, so one buffer serves them all.
-int verify_flags_host(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
-                      size_t parity_block_stride, size_t S, size_t nblocks, uint32_t* bad_out) {
-    if (!c || !data || !parity || !bad_out) return RSMI_ERR_INVALID_ARG;
-    if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
-    if (data_block_stride < size_t(c->k) * S || parity_block_stride < size_t(c->m) * S) return RSMI_ERR_INVALID_ARG;
-    if (nblocks == 0) return RSMI_OK;
-    const size_t m = size_t(c->m), flag_bytes = nblocks * m * sizeof(uint32_t);
-    uint32_t* d_bad = nullptr;
-    StripeCheck chk;
-    chk.prepare = [&]() -> int {
-        int rc = reserve(c->d_vbad, c->vbad_cap, flag_bytes);
-        d_bad = reinterpret_cast<uint32_t*>(c->d_vbad);
+// The results live in device memory on every path (no atomics aimed at host memory); every host
+// call synchronises before it returns, so one buffer serves them all.
+void stripe_results(rsmi_ctx* c, size_t nblocks, int32_t* culprit_out, uint32_t* bad_out, StripeResults& r,
+                    StripeCheck& chk) {
+    const size_t flag_bytes = nblocks * size_t(c->m) * sizeof(uint32_t);
+    const size_t verdict_bytes = culprit_out ? nblocks * sizeof(int32_t) : 0;
+    chk.prepare = [=, &r]() -> int {
+        int rc = reserve(c->d_vbad, c->vbad_cap, flag_bytes + verdict_bytes);
+        r.d_bad = reinterpret_cast<uint32_t*>(c->d_vbad);
+        r.d_culprit = reinterpret_cast<int32_t*>(r.d_bad + nblocks * size_t(c->m));
         return rc;
     };
+    chk.fetch = [=, &r](hipStream_t st) -> int {
+        if (st) {
+            if (culprit_out) HIP_TRY(hipMemcpyAsync(culprit_out, r.d_culprit, verdict_bytes, hipMemcpyDeviceToHost, st));
+            if (bad_out) HIP_TRY(hipMemcpyAsync(bad_out, r.d_bad, flag_bytes, hipMemcpyDeviceToHost, st));
+        } else {
+            if (culprit_out) HIP_TRY(hipMemcpy(culprit_out, r.d_culprit, verdict_bytes, hipMemcpyDeviceToHost));
+            if (bad_out) HIP_TRY(hipMemcpy(bad_out, r.d_bad, flag_bytes, hipMemcpyDeviceToHost));
+        }
+        return RSMI_OK;
+    };
+}
+
+int check_stripe_dev_args(const rsmi_ctx* c, const void* d_data, size_t data_shard_stride, const void* d_parity,
+                          size_t parity_shard_stride, size_t S, const void* out) {
+    if (!c || !d_data || !d_parity || !out) return RSMI_ERR_INVALID_ARG;
+    if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
+    if (data_shard_stride < S || parity_shard_stride < S) return RSMI_ERR_INVALID_ARG;
+    return RSMI_OK;
+}
+
+int check_stripe_host_args(const rsmi_ctx* c, const void* data, size_t data_block_stride, const void* parity,
+                           size_t parity_block_stride, size_t S, const void* out) {
+    if (!c || !data || !parity || !out) return RSMI_ERR_INVALID_ARG;
+    if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
+    if (data_block_stride < size_t(c->k) * S || parity_block_stride < size_t(c->m) * S) return RSMI_ERR_INVALID_ARG;
+    return RSMI_OK;
+}
+
+int begin_stripe_dev_call(rsmi_ctx* c, std::unique_lock<std::mutex>& lock, std::shared_ptr<Plan>& plan) {
+    lock = std::unique_lock<std::mutex>(c->mu);
+    int rc = ensure_device(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return encode_plan(c, plan);
+}
+
+namespace {
+
+// Host-memory verify on verify_host_impl's paths: flags alone.
+int verify_flags_host(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
+                      size_t parity_block_stride, size_t S, size_t nblocks, uint32_t* bad_out) {
+    if (int rc = check_stripe_host_args(c, data, data_block_stride, parity, parity_block_stride, S, bad_out)) return rc;
+    if (nblocks == 0) return RSMI_OK;
+    const size_t m = size_t(c->m);
+    StripeResults r;
+    StripeCheck chk;
+    stripe_results(c, nblocks, nullptr, bad_out, r, chk);
     chk.launch = [&](const Plan& plan, const uint8_t* d, uint64_t d_rs, uint64_t d_bs, const uint8_t* p, uint64_t p_rs,
                      uint64_t p_bs, uint64_t nb, uint64_t b0, hipStream_t st) -> int {
-        return launch_verify(c, plan, d, d_rs, d_bs, p, p_rs, p_bs, S, nb, d_bad + b0 * m, st);
-    };
-    chk.fetch = [&](hipStream_t st) -> int {
-        if (st)
-            HIP_TRY(hipMemcpyAsync(bad_out, d_bad, flag_bytes, hipMemcpyDeviceToHost, st));
-        else
-            HIP_TRY(hipMemcpy(bad_out, d_bad, flag_bytes, hipMemcpyDeviceToHost));
-        return RSMI_OK;
+        return launch_verify(c, plan, d, d_rs, d_bs, p, p_rs, p_bs, S, nb, r.d_bad + b0 * m, st);
     };
     return verify_host_impl(c, data, data_block_stride, parity, parity_block_stride, S, nblocks, chk);
 }
@@ -277,17 +331,12 @@ extern "C" {
 int rsmi_verify_batch_dev(rsmi_ctx* c, const uint8_t* d_data, size_t data_shard_stride, size_t data_block_stride,
                           const uint8_t* d_parity, size_t parity_shard_stride, size_t parity_block_stride, size_t S,
                           size_t nblocks, uint32_t* d_bad_out, void* stream) try {
-    if (!c || !d_data || !d_parity || !d_bad_out) return RSMI_ERR_INVALID_ARG;
-    if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
-    if (data_shard_stride < S || parity_shard_stride < S) return RSMI_ERR_INVALID_ARG;
+    int rc = check_stripe_dev_args(c, d_data, data_shard_stride, d_parity, parity_shard_stride, S, d_bad_out);
+    if (rc) return rc;
     if (nblocks == 0) return RSMI_OK;
     std::shared_ptr<Plan> plan;
-    std::lock_guard<std::mutex> g(c->mu);
-    int rc = ensure_device(c);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    rc = encode_plan(c, plan);
-    if (rc) return rc;
+    std::unique_lock<std::mutex> lock;
+    if ((rc = begin_stripe_dev_call(c, lock, plan))) return rc;
     return launch_verify(c, *plan, d_data, data_shard_stride, data_block_stride, d_parity, parity_shard_stride,
                          parity_block_stride, S, nblocks, d_bad_out, static_cast<hipStream_t>(stream));
 } catch (...) {

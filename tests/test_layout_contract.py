@@ -328,15 +328,15 @@ def test_phases_case_rotates_the_rows():
             assert all(differ) if w > 1 else any(differ), (k, m, S, differ)
 
 
-def _body(src, name):
-    a = src.index("\nint %s(" % name)
+def _body(src, name, ret="int"):
+    a = src.index("\n%s %s(" % (ret, name))
     return " ".join(src[a:src.index("\n}\n", a)].split())
 
 
 def test_predicate_matches_source():
-    """expected_form() is what launch_plan, launch_plan_crc and launch_verify say, and the host
-    path rule of leg 4 is what encode_host_impl says: an edit to any of them fails here instead of
-    silently retargeting the cases."""
+    """expected_form() is what launch_plan, launch_plan_crc and stripe_layout (launch_verify's
+    test) say, and the host path rule of leg 4 is what encode_host_impl says: an edit to any of them
+    fails here instead of silently retargeting the cases."""
     with open(os.path.join(CSRC, "rsmi_core.cpp")) as f:
         plan = _body(f.read(), "launch_plan")
     with open(os.path.join(CSRC, "rsmi_crc.cpp")) as f:
@@ -347,7 +347,11 @@ def test_predicate_matches_source():
         host = _body(f.read(), "encode_host_impl")
     with open(os.path.join(CSRC, "rsmi_impl.hpp")) as f:
         impl = f.read()
-    plan_crc, verify = _body(crc_src, "launch_plan_crc"), _body(ver_src, "launch_verify")
+    plan_crc, verify = _body(crc_src, "launch_plan_crc"), _body(ver_src, "stripe_layout", "StripeLayout")
+    scratch = _body(ver_src, "encode_into_scratch")
+    launch = _body(ver_src, "launch_verify")
+    assert "stripe_layout(data, data_rs, data_bs, parity, parity_rs, parity_bs, S)" in launch
+    assert "{&enc, &enc_rs, &enc_bs, &parb, &parity_rs, &parity_bs, &S, &m32, &nb, &badb}" in launch
     assert ("const bool aligned = ((reinterpret_cast<uintptr_t>(in) | tba) % 16 == 0) && "
             "((reinterpret_cast<uintptr_t>(out) | tba) % 16 == 0) && in_rs % 16 == 0 && in_bs % 16 == 0 && "
             "out_rs % 16 == 0 && out_bs % 16 == 0 && in_rs >= round_up(S, 16) && out_rs >= round_up(S, 16) && "
@@ -368,8 +372,8 @@ def test_predicate_matches_source():
         assert body.count("const bool aligned =") == 1 and body.count("const bool ua =") == 1
     assert "inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }" in impl
     # the fallback of the verify compares scratch rows at pitch round_up(S, 16) with the stored ones
-    assert "const uint64_t Sp = round_up(S, 16);" in verify
-    assert "uint64_t enc_bs = m * Sp, enc_rs = Sp, n = nb;" in verify
+    assert "const uint64_t Sp = round_up(S, 16);" in scratch
+    assert "const uint64_t enc_bs = m * Sp, enc_rs = Sp;" in scratch and "fn(b0, nb, vs.p, enc_rs, enc_bs)" in scratch
     # the entry points hand the caller's six numbers on unchanged, in the header's order
     tail = ("d_data, data_shard_stride, data_block_stride, d_parity, parity_shard_stride, parity_block_stride, "
             "S, nblocks, ")
