@@ -1,7 +1,9 @@
 """Seeded random-shape parity sweep on the GPU: random (k, m), shard sizes, batch sizes,
 layouts (aligned pitches, padded strides, unaligned offsets) and erasure patterns, every
 result compared byte for byte with the CPU oracle.  Complements the fixed grids of
-test_gpu_parity.py with shapes nobody picked by hand."""
+test_gpu_parity.py with shapes nobody picked by hand.  The last part does the same for verify,
+locate and heal: random shapes, sizes, independent data and parity layouts and damage per block,
+against the definition."""
 import numpy as np
 import pytest
 
@@ -222,3 +224,243 @@ def test_random_lone_in_place_calls(seed):
                     assert [rsmi.crc16_entry(b"", int(v16[j]), S) for j in range(k)] == [r16[i] for i in used]
     finally:
         L.rsmi_host_free(p)
+
+
+# ---------------------------------------------------------------- verify, locate and heal
+# Seeded random stripe checks: shapes and sizes nobody picked (K = 7, 17 and 20, m = 5..8, rows
+# shorter than 16 bytes and just past a tile), the two sides in layouts drawn independently, in one
+# allocation or two, and the damage of every block drawn from DAMAGE.  The expected flags, verdicts
+# and image are the definition's (test_verify.want_flags, test_locate.want_verdicts,
+# test_heal.want_image, all on the CPU oracle); the labels are test_stripe_layouts.stripe_labels'.
+STRIPE_CASES = 48
+STRIPE_KS = [1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 16, 17, 20]
+STRIPE_MS = [1, 1, 2, 2, 2, 3, 3, 3, 4, 4, 4, 5, 6, 7, 8]
+LAYOUTS = ["pitched", "padded", "odd", "packed"]
+LAYOUT_P = [0.3, 0.3, 0.2, 0.2]
+DAMAGE = ["none", "padding", "one-byte", "burst", "stale-row", "one-shard-tiles", "two-shards-column",
+          "two-shards-tiles", "two-parity-rows"]
+_STRIPE = {}
+
+
+def _stripe_side(layout, alloc, rows, S, nb, base):
+    """One side's rows from offset base (a multiple of 16) of its allocation's payload."""
+    from test_layout_contract import Side
+
+    R = (S + 15) // 16 * 16
+    if layout == "pitched":      # rsmi.recommended_pitch from an aligned base
+        rs = rsmi.recommended_pitch(S)
+        return Side(alloc, base, rs, rows * rs)
+    if layout == "padded":       # round_up(S, 16) + 48, a block gap of 16
+        return Side(alloc, base, R + 48, rows * (R + 48) + 16)
+    if layout == "odd":          # rs = S + 3 from offset 7
+        return Side(alloc, base + 7, S + 3, rows * (S + 3))
+    return Side(alloc, base, S, rows * S)   # rs = S, back to back
+
+
+def _burst(S):
+    """A run of bytes across a 16-byte and a 1024-byte boundary, as far as the row reaches."""
+    if S >= 1030:
+        return 1003, min(S, 1045)
+    if S > 16:
+        return max(0, 16 - 9), min(S, 16 + 9)
+    return 0, S
+
+
+def _damage(r, kind, sh, k, m, S):
+    """Damage one block's rows sh (n, S) in place; "none" and "padding" leave them alone."""
+    n = k + m
+
+    def val(size=None):
+        return r.integers(1, 256, size=size, dtype=np.uint8)
+
+    far = [p for p in (5, 1030, 2100, 4200, 9000, 19000) if p < S] or [0]
+    if kind == "one-byte":
+        sh[int(r.integers(0, n)), int(r.integers(0, S))] ^= val()
+    elif kind == "burst":
+        lo, hi = _burst(S)
+        sh[int(r.integers(0, n)), lo:hi] ^= val(hi - lo)
+    elif kind == "stale-row":
+        sh[int(r.integers(0, n))] = r.integers(0, 256, size=S, dtype=np.uint8)
+    elif kind == "one-shard-tiles":
+        x = int(r.integers(0, n))
+        for p in far + [S - 1]:
+            sh[x, p] ^= val()
+    elif kind in ("two-shards-column", "two-shards-tiles"):
+        x0, x1 = (int(x) for x in r.choice(n, size=2, replace=False))
+        p0 = int(r.integers(0, S))
+        p1 = p0 if kind == "two-shards-column" else (p0 + max(1, min(S - 1, 1024 + int(r.integers(0, 2000))))) % S
+        sh[x0, p0] ^= val()
+        sh[x1, p1] ^= val()
+    elif kind == "two-parity-rows":
+        js = r.choice(m, size=min(2, m), replace=False)
+        p0 = int(r.integers(0, S))
+        for j in js:
+            sh[k + int(j), p0] ^= val()
+
+
+def _stripe_case(seed):
+    """Everything a case needs, the definition's answers included, computed once per seed."""
+    if seed in _STRIPE:
+        return _STRIPE[seed]
+    from test_heal import want_image
+    from test_layout_contract import GUARD, blank, expected_form, put, row_at
+    from test_locate import want_verdicts
+    from test_verify import want_flags
+
+    r = np.random.default_rng(77000 + seed)
+    k = int(r.choice(STRIPE_KS))
+    m = int(r.choice(STRIPE_MS))
+    # U(1, 16) is there for the rows shorter than 16 bytes: U(1, 5000) draws one in 300 cases
+    S = int(r.choice([16, 17, 31, int(r.integers(1, 16)), int(r.integers(1, 5000)), int(r.integers(5000, 20001))]))
+    nb = int(r.integers(1, 7))
+    dlay, play = (str(x) for x in r.choice(LAYOUTS, size=2, p=LAYOUT_P))
+    one_alloc = bool(r.integers(0, 2))
+    wpc1 = bool(r.integers(0, 4) == 0)
+    d = _stripe_side(dlay, "x" if one_alloc else "d", k, S, nb, 0)
+    pbase = (d.off + nb * d.bs + 15) // 16 * 16 + 32 if one_alloc else 0
+    p = _stripe_side(play, "x" if one_alloc else "p", m, S, nb, pbase)
+    data = r.integers(0, 256, size=(nb, k, S), dtype=np.uint8)
+    sh = np.concatenate([data, orc.encode_fast(k, m, data, threads=4)], axis=1)
+    kinds = [str(x) for x in r.choice(DAMAGE, size=nb)]
+    for b in range(nb):
+        _damage(r, kinds[b], sh[b], k, m, S)
+    before = blank(d, p, nb)
+    put(before, d, sh[:, :k])
+    put(before, p, sh[:, k:])
+    for b in range(nb):
+        if kinds[b] != "padding":
+            continue
+        # a byte that belongs to no row: after a row where the pitch leaves one, in the gap behind
+        # a block, or in the guard in front of the side's first row
+        spots = []
+        for side, rows in ((d, k), (p, m)):
+            if side.rs > S:
+                spots.append((side.alloc, row_at(side, b, int(r.integers(0, rows))) + S))
+            if side.bs > rows * side.rs:
+                spots.append((side.alloc, row_at(side, b, 0) + rows * side.rs))
+            spots.append((side.alloc, row_at(side, 0, 0) - 1))
+        a, o = spots[int(r.integers(0, len(spots)))]
+        before[a][o] ^= 0xFF
+    verdicts = want_verdicts(k, m, sh)
+    image = want_image(k, m, sh, verdicts)
+    want = {a: x.copy() for a, x in before.items()}
+    put(want, d, image[:, :k])
+    put(want, p, image[:, k:])
+    form = expected_form(GUARD + d.off, d.rs, d.bs, GUARD + p.off, p.rs, p.bs, S)  # from 16-byte-aligned allocations
+    case = dict(k=k, m=m, S=S, nb=nb, d=d, p=p, wpc1=wpc1, kinds=kinds, sh=sh, before=before, want=want, form=form,
+                verdicts=verdicts, flags=want_flags(k, m, sh), image_flags=want_flags(k, m, image))
+    _STRIPE[seed] = case
+    return case
+
+
+def test_stripe_generator_coverage():
+    """The committed seed range reaches what the fuzz is there for (conditions on the generator,
+    not measurements): every family of heal's labels, rows shorter than 16 bytes, every damage
+    kind, every kind of verdict as the definition gives it, and the two sides at different shard
+    strides in at least half the cases."""
+    import collections
+
+    from test_locate import CLEAN, UNKNOWN
+    from test_stripe_layouts import family, stripe_labels
+
+    fam, kinds, verdicts = collections.Counter(), collections.Counter(), collections.Counter()
+    short = differ = 0
+    for seed in range(STRIPE_CASES):
+        c = _stripe_case(seed)
+        k, m, S, d, p = c["k"], c["m"], c["S"], c["d"], c["p"]
+        assert d.rs >= S and p.rs >= S and d.bs >= k * d.rs and p.bs >= m * p.rs
+        assert d.alloc != p.alloc or d.off + c["nb"] * d.bs <= p.off
+        label = stripe_labels(k, m, c["form"])[2]
+        fam["m=1" if m == 1 else family(label)] += 1
+        short += S < 16
+        differ += d.rs != p.rs
+        kinds.update(c["kinds"])
+        for v in c["verdicts"].tolist():
+            verdicts["clean" if v == CLEAN else "unknown" if v == UNKNOWN else "data" if v < k else "parity"] += 1
+        # an UNKNOWN block alone keeps flags in the image
+        assert np.array_equal(c["image_flags"].any(axis=1), c["verdicts"] == UNKNOWN), seed
+    print("\nstripe fuzz generator: families", dict(fam), "damage", dict(kinds), "verdicts", dict(verdicts),
+          "S < 16:", short, "sides differ in shard stride:", differ)
+    assert fam["fused"] >= 5 and fam["fused,UA"] >= 5 and fam["rows"] >= 5 and fam["m=1"] >= 2, dict(fam)
+    assert short >= 2, short
+    for kind in DAMAGE:
+        assert kinds[kind] >= 6, (kind, dict(kinds))
+    for v in ("clean", "data", "parity", "unknown"):
+        assert verdicts[v] >= 10, (v, dict(verdicts))
+    assert 2 * differ >= STRIPE_CASES, differ
+
+
+_STRIPE_SEEN = {}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", range(STRIPE_CASES))
+def test_random_stripe_checks(seed):
+    """On one context: verify (flags), locate (verdicts, flags, nothing written), heal (verdicts,
+    flags, the whole buffers against the definition's image), and verify again on the healed
+    device buffers (flags only where the verdict was UNKNOWN).  Every call's label is the rule's,
+    evaluated on the pointers the call really got."""
+    import collections
+
+    import torch
+
+    from test_layout_contract import check, download, dptr, expected_form, upload
+    from test_locate import UNKNOWN
+    from test_stripe_layouts import family, stripe_labels
+
+    c = _stripe_case(seed)
+    k, m, S, nb, d, p = c["k"], c["m"], c["S"], c["nb"], c["d"], c["p"]
+    ctx = (seed, k, m, S, nb, tuple(d), tuple(p), c["wpc1"], c["kinds"])
+    st = torch.cuda.current_stream().cuda_stream
+    dev = upload(torch, c["before"])
+    args = (dptr(dev, d), d.rs, d.bs, dptr(dev, p), p.rs, p.bs, S, nb)
+    form = expected_form(dptr(dev, d), d.rs, d.bs, dptr(dev, p), p.rs, p.bs, S)
+    assert form == c["form"], ctx
+    vlabel, llabel, hlabel = stripe_labels(k, m, form)
+
+    def outputs():
+        return (torch.full((nb + 2,), 0x5EED, dtype=torch.int32, device="cuda"),
+                torch.full((nb * m + 2,), 0x5EED, dtype=torch.int32, device="cuda"))
+
+    def results(cul, bad):
+        cul, bad = cul.cpu().numpy(), bad.cpu().numpy()
+        assert (cul[nb:] == 0x5EED).all() and (bad[nb * m:] == 0x5EED).all(), ctx
+        return cul[:nb], bad[:nb * m].reshape(nb, m) != 0
+
+    with rsmi.Codec(k, m) as cd:
+        if c["wpc1"]:
+            cd.set_option("waves_per_cu", 1)
+        cul, bad = outputs()
+        cd.verify_batch_dev(*args, bad.data_ptr(), st)
+        torch.cuda.synchronize()
+        assert cd.last_kernel() == vlabel, (cd.last_kernel(), vlabel) + ctx
+        assert np.array_equal(results(cul, bad)[1], c["flags"]), ctx
+
+        cul, bad = outputs()
+        cd.locate_batch_dev(*args, cul.data_ptr(), bad.data_ptr(), st)
+        torch.cuda.synchronize()
+        assert cd.last_kernel() == llabel, (cd.last_kernel(), llabel) + ctx
+        got, gbad = results(cul, bad)
+        assert np.array_equal(got, c["verdicts"]), ctx + (got.tolist(), c["verdicts"].tolist())
+        assert np.array_equal(gbad, c["flags"]), ctx
+        check(download(dev), c["before"], ctx + ("locate wrote to the shards",))
+
+        cul, bad = outputs()
+        vcul, vbad = outputs()
+        cd.heal_batch_dev(*args, cul.data_ptr(), bad.data_ptr(), st)
+        healed_by = cd.last_kernel()
+        cd.verify_batch_dev(*args, vbad.data_ptr(), st)
+        torch.cuda.synchronize()
+        assert healed_by == hlabel, (healed_by, hlabel) + ctx
+        assert cd.last_kernel() == vlabel, (cd.last_kernel(), vlabel) + ctx
+        got, gbad = results(cul, bad)
+        assert np.array_equal(got, c["verdicts"]), ctx + (got.tolist(), c["verdicts"].tolist())
+        assert np.array_equal(gbad, c["flags"]), ctx
+        check(download(dev), c["want"], ctx)
+        after = results(vcul, vbad)[1]
+        assert np.array_equal(after, c["image_flags"]), ctx + (after.tolist(),)
+        assert np.array_equal(after.any(axis=1), c["verdicts"] == UNKNOWN), ctx
+    _STRIPE_SEEN.setdefault("heal", collections.Counter())["m=1" if m == 1 else family(hlabel)] += 1
+    _STRIPE.pop(seed, None)
+    if seed == STRIPE_CASES - 1:
+        print("\nstripe fuzz: heal calls run and asserted by label, per family:", dict(_STRIPE_SEEN["heal"]))

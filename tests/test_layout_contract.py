@@ -773,9 +773,9 @@ class HostBuf:
     """nb blocks of nrows rows of S bytes at block stride bs, 64 guard bytes before and after, in
     pageable or page-locked (rsmi_host_alloc) memory."""
 
-    def __init__(self, rsmi, nrows, S, bs, fill, pinned):
+    def __init__(self, rsmi, nrows, S, bs, fill, pinned, nb=NB):
         self.rsmi, self.side, self.nrows = rsmi, Side("h", 0, S, bs), nrows
-        size = GUARD + NB * bs + GUARD
+        size = GUARD + nb * bs + GUARD
         self.p = None
         if pinned:
             self.p = rsmi.lib().rsmi_host_alloc(size)
