@@ -201,6 +201,19 @@ struct HealKernelTable {
 const HealKernelTable& heal_kernels();
 void* heal_rows_kernel();
 
+// rsmi_reconstruct_mixed_batch_* (rs_mixed_kernels.hip): rs_mixed_kernel per (K, MT), the K of
+// the verify kernels, aligned and unaligned-window layouts (null when the shape has none).  A
+// launch codes the tiles of one class of blocks: entry e of its list names the block and, through
+// the launch's array of plan pointers, the one-tile plan (MT output rows) of that block's pattern.
+struct MixedEntry {
+    uint32_t blk, pat;
+};
+struct MixedKernelTable {
+    void* fn[17][kMaxMT + 1];
+    void* ua[17][kMaxMT + 1];
+};
+const MixedKernelTable& mixed_kernels();
+
 // CRC-16 of shard rows (crc16.hpp): the device table buffer holds P[15][2][256] (the powers
 // A^(2^i), byte-sliced) and N[32][16] (u16); a wave folds kCrcSegTiles 1 KiB tiles of one row
 // with one N lookup per nibble (16-entry tables: each wave-wide lookup touches 8 distinct

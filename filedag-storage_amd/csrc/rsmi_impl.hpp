@@ -8,9 +8,10 @@
 //                      fallback, the host paths, the entry points' checks and prologue
 //   rsmi_locate.cpp    rsmi_locate: the shard that breaks a stripe, from Verify's syndromes
 //   rsmi_heal.cpp      rsmi_heal: locate, then the named shard rewritten on the same stream
+//   rsmi_mixed.cpp     rsmi_reconstruct_mixed_*: a batch whose blocks each have their own erasure pattern
 // No CPU compute path anywhere: every byte of parity, reconstructed data or CRC and every verify
 // flag comes out of the HIP kernels (rs_kernels.hip, rs_kernels_tb.hip, rs_crc16_kernels.hip, rs_crc32_kernels.hip,
-// rs_verify_kernels.hip, rs_locate_kernels.hip, rs_heal_kernels.hip).
+// rs_verify_kernels.hip, rs_locate_kernels.hip, rs_heal_kernels.hip, rs_mixed_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -151,6 +152,17 @@ struct rsmi_ctx {
     // caller takes none) of its launches; the fallback kernel's tables, uploaded on first use
     std::map<hipStream_t, VerifyScratch> locate_scratch;
     uint8_t* d_locate_tbl = nullptr;
+    // rsmi_reconstruct_mixed_batch_* (rsmi_mixed.cpp): per stream the class lists and plan
+    // pointers of its launches.  A call's words are written to the page-locked half h at head and
+    // copied from there to the same offset of the device half d, both on that stream; head moves
+    // on, so an earlier call's words stay until its copy and kernels have consumed them.  When a
+    // call's words no longer fit behind head, the stream is waited for once and head starts over.
+    struct MixedScratch {
+        uint8_t* d = nullptr;
+        uint8_t* h = nullptr;
+        size_t cap = 0, head = 0;
+    };
+    std::map<hipStream_t, MixedScratch> mixed_scratch;
     rsmi::Crc32Shift crc32_shift{};  // launch_crc32's per-S shift matrix, for crc32_shift_S
     uint64_t crc32_shift_S = ~uint64_t(0);
     CrcScratch own_scratch;  // the fused encode + CRC-16's scratch on the context's own streams
@@ -357,6 +369,24 @@ int launch_locate(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t d
 // (ctx->d_locate_tbl: log | exp | R | inv(M[k][c])), both built on first use
 int ratio_plan(rsmi_ctx* c, std::shared_ptr<Plan>& out);
 int ensure_locate_tables(rsmi_ctx* c);
+// rsmi_reconstruct_mixed_* (rsmi_mixed.cpp).  The host classing of a call, device-free: the
+// blocks' distinct (present, want) pairs, numbered by first appearance, and per block its pair,
+// its status and the number of rows the call writes in it.  A pair's key holds per row bit 0
+// (present) and bit 1 (the row is rebuilt: wanted and missing).
+struct MixedBatch {
+    std::vector<std::string> keys;  // per pattern
+    std::vector<uint8_t> key_rows;  // ... the rows it rebuilds, 0 also where too few rows are present
+    std::vector<int32_t> key_status;
+    std::vector<uint32_t> pat;  // per block
+    size_t work = 0, too_few = 0;  // blocks with rows to rebuild; blocks with too few rows present
+};
+void classify_mixed(const rsmi_ctx* c, size_t nblocks, const uint8_t* present, const uint8_t* required, int data_only,
+                    MixedBatch& mb);
+// The launches of blocks [b0, b0 + nb) of a classed batch (caller holds ctx->mu, the device is
+// bound): rs_mixed_kernel per class, launch_plan per run of fallback blocks.  base: block b0's
+// first row.  Stream-ordered, no synchronisation unless the stream's scratch grows or wraps.
+int launch_mixed(rsmi_ctx* c, const MixedBatch& mb, uint8_t* base, uint64_t rs, uint64_t bs, uint64_t S, uint64_t b0,
+                 uint64_t nb, hipStream_t stream);
 int ensure_crc_tables(rsmi_ctx* c);
 int ensure_crc32_tables(rsmi_ctx* c);
 // R(row) / R32(row) of the rows the plan rebuilt (want && !present), one row per block at

@@ -1,0 +1,359 @@
+// rsmi_mixed.cpp -- rsmi_reconstruct_mixed_* (include/rsmi.h; see rsmi_impl.hpp for the file map):
+// the in-place reconstruct of a batch in which every block has its own present (and required)
+// mask.  The host deduplicates the blocks' (present, want) pairs, takes each pair's plan from the
+// cache the uniform call uses (reconstruct_plan), sorts the blocks into classes by the number of
+// rows their plan rebuilds (1..4) and launches rs_mixed_kernel (rs_mixed_kernels.hip) once per
+// class over that class's tiles; a wave finds its block and plan through the class's list.
+// Blocks whose plan has more than one tile, whose K has no rs_mixed_kernel, or whose layout is
+// neither aligned nor unaligned-window take the uniform call's launch_plan, one per run of
+// consecutive blocks with equal masks: the correctness path of rare shapes.
+
+#include "rsmi_impl.hpp"
+
+#include <limits>
+#include <unordered_map>
+
+using namespace rsmi;
+using namespace rsmi::impl;
+
+namespace rsmi {
+namespace impl {
+
+void classify_mixed(const rsmi_ctx* c, size_t nblocks, const uint8_t* present, const uint8_t* required, int data_only,
+                    MixedBatch& mb) {
+    const size_t n = size_t(c->n), k = size_t(c->k);
+    mb = MixedBatch();
+    mb.pat.resize(nblocks);
+    std::unordered_map<std::string, uint32_t> index;
+    std::string key(n, '0');
+    uint32_t last = 0;
+    for (size_t b = 0; b < nblocks; b++) {
+        const uint8_t* p = present + b * n;
+        const uint8_t* r = required ? required + b * n : nullptr;
+        for (size_t i = 0; i < n; i++) {
+            const bool have = p[i] != 0;
+            const bool want = !have && (r ? r[i] != 0 : (i < k || !data_only));
+            key[i] = char('0' + (have ? 1 : 0) + (want ? 2 : 0));
+        }
+        // neighbours mostly share their masks: the map is asked once per run
+        if (b == 0 || key != mb.keys[last]) {
+            auto it = index.find(key);
+            if (it == index.end()) {
+                size_t np = 0, rows = 0;
+                for (size_t i = 0; i < n; i++) {
+                    np += key[i] == '1';
+                    rows += key[i] == '2';
+                }
+                // upstream reconstruct(): nothing wanted is missing -> no-op; then fewer than k present
+                const bool few = rows != 0 && np < k;
+                it = index.emplace(key, uint32_t(mb.keys.size())).first;
+                mb.keys.push_back(key);
+                mb.key_status.push_back(few ? RSMI_ERR_TOO_FEW_SHARDS : RSMI_OK);
+                mb.key_rows.push_back(few ? 0 : uint8_t(rows));
+            }
+            last = it->second;
+        }
+        mb.pat[b] = last;
+        if (mb.key_status[last] != RSMI_OK) mb.too_few++;
+        else if (mb.key_rows[last]) mb.work++;
+    }
+}
+
+namespace {
+
+constexpr int kNoLaunch = 0, kFallback = -1;  // a pattern's class, beside 1..kMaxMT
+
+// The stream's entry of ctx->mixed_scratch (caller holds ctx->mu), evicted past 32 streams as
+// stream_scratch (rsmi_verify.cpp) evicts.
+rsmi_ctx::MixedScratch& mixed_scratch(rsmi_ctx* c, hipStream_t st) {
+    auto& map = c->mixed_scratch;
+    auto it = map.find(st);
+    if (it != map.end()) return it->second;
+    if (map.size() >= 32) {
+        (void)hipDeviceSynchronize();
+        for (auto& e : map) {
+            if (e.second.d) (void)hipFree(e.second.d);
+            if (e.second.h) (void)hipHostFree(e.second.h);
+        }
+        map.clear();
+    }
+    return map[st];
+}
+
+// need bytes of the stream's scratch, 16-byte aligned, at the same offset of both halves; they
+// stay untouched until the stream has been waited for.  Waits for the stream once when the
+// scratch has to grow or start over.
+int mixed_words(rsmi_ctx* c, hipStream_t st, size_t need, uint8_t*& h, uint8_t*& d) {
+    rsmi_ctx::MixedScratch& ms = mixed_scratch(c, st);
+    need = round_up(need, 16);
+    if (ms.cap - ms.head < need) {
+        if (ms.d) HIP_TRY(hipStreamSynchronize(st));
+        ms.head = 0;
+        if (ms.cap < need) {
+            const size_t cap = std::max<size_t>(std::max(need, ms.cap + ms.cap / 2), size_t(1) << 20);
+            if (ms.d) HIP_TRY(hipFree(ms.d));
+            ms.d = nullptr;
+            if (ms.h) HIP_TRY(hipHostFree(ms.h));
+            ms.h = nullptr;
+            ms.cap = 0;
+            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ms.d), cap));
+            HIP_TRY(pinned_alloc(reinterpret_cast<void**>(&ms.h), cap));
+            ms.cap = cap;
+        }
+    }
+    h = ms.h + ms.head;
+    d = ms.d + ms.head;
+    ms.head += need;
+    return RSMI_OK;
+}
+
+}  // namespace
+
+int launch_mixed(rsmi_ctx* c, const MixedBatch& mb, uint8_t* base, uint64_t rs, uint64_t bs, uint64_t S, uint64_t b0,
+                 uint64_t nb, hipStream_t stream) {
+    if (nb == 0 || S == 0) return RSMI_OK;
+    const size_t n = size_t(c->n), npat = mb.keys.size();
+    // launch_plan's layout test, the rows being read and written in place
+    const StripeLayout layout = stripe_layout(base, rs, bs, base, rs, bs, S);
+    const bool aligned = layout == StripeLayout::kAligned;
+    const uint64_t cpb = (S + 15) / 16;
+    const uint64_t tpb = (cpb + uint64_t(kWave) - 1) / uint64_t(kWave);
+    constexpr int wpg = kFastWG / kWave;
+    long wg_cap = std::numeric_limits<long>::max();
+    if (c->opt_waves_per_cu > 0) wg_cap = std::max(1L, long(c->num_cu) * c->opt_waves_per_cu / wpg);
+
+    // per pattern that has a block here: its plan and its class
+    std::vector<std::shared_ptr<Plan>> plans(npat);
+    std::vector<int> cls(npat, kNoLaunch);
+    std::vector<uint8_t> seen(npat, 0);
+    std::vector<uint8_t> have(n), want(n);
+    const int K = c->k;  // every reconstruct plan reads k survivors
+    for (uint64_t b = b0; b < b0 + nb; b++) {
+        const uint32_t p = mb.pat[b];
+        if (seen[p]) continue;
+        seen[p] = 1;
+        if (!mb.key_rows[p]) continue;
+        for (size_t i = 0; i < n; i++) {
+            have[i] = mb.keys[p][i] == '1';
+            want[i] = mb.keys[p][i] == '2';
+        }
+        int rc = reconstruct_plan(c, have.data(), want.data(), plans[p]);
+        if (rc) return rc;
+        const Plan& pl = *plans[p];
+        const DevTile& t = pl.tiles[0];
+        const bool fast = layout != StripeLayout::kNeither && pl.tiles.size() == 1 && t.K == K && K <= 16 &&
+                          (aligned ? mixed_kernels().fn : mixed_kernels().ua)[K][t.MT] != nullptr;
+        cls[p] = fast ? t.MT : kFallback;
+    }
+
+    // segments whose block indices and whose tile counts per class fit 32 bits
+    const uint64_t seg = std::min<uint64_t>(std::max<uint64_t>(1, (uint64_t(1) << 31) / tpb), uint64_t(1) << 22);
+    std::vector<MixedEntry> list[kMaxMT + 1];
+    for (uint64_t s0 = b0; s0 < b0 + nb; s0 += seg) {
+        const uint64_t sn = std::min(seg, b0 + nb - s0);
+        uint8_t* sbase = base + (s0 - b0) * bs;
+        for (auto& l : list) l.clear();
+        size_t nfast = 0;
+        for (uint64_t b = 0; b < sn; b++) {
+            const uint32_t p = mb.pat[s0 + b];
+            if (cls[p] > 0) {
+                list[cls[p]].push_back(MixedEntry{uint32_t(b), p});
+                nfast++;
+            }
+        }
+        if (nfast) {
+            // one upload: the patterns' plan pointers, then the classes' lists in ascending MT
+            const size_t ptr_bytes = round_up(npat * sizeof(const RsPlanDev*), 16);
+            uint8_t *h = nullptr, *d = nullptr;
+            int rc = mixed_words(c, stream, ptr_bytes + nfast * sizeof(MixedEntry), h, d);
+            if (rc) return rc;
+            auto* hp = reinterpret_cast<const RsPlanDev**>(h);
+            for (size_t p = 0; p < npat; p++) hp[p] = cls[p] > 0 ? plans[p]->tiles[0].dev : nullptr;
+            size_t off = ptr_bytes;
+            size_t list_off[kMaxMT + 1] = {};
+            for (int mt = 1; mt <= kMaxMT; mt++) {
+                list_off[mt] = off;
+                if (!list[mt].empty()) std::memcpy(h + off, list[mt].data(), list[mt].size() * sizeof(MixedEntry));
+                off += list[mt].size() * sizeof(MixedEntry);
+            }
+            HIP_TRY(hipMemcpyAsync(d, h, off, hipMemcpyHostToDevice, stream));
+            for (int mt = 1; mt <= kMaxMT; mt++) {
+                if (list[mt].empty()) continue;
+                void* fn = (aligned ? mixed_kernels().fn : mixed_kernels().ua)[K][mt];
+                const MixedEntry* dl = reinterpret_cast<const MixedEntry*>(d + list_off[mt]);
+                const RsPlanDev* const* dp = reinterpret_cast<const RsPlanDev* const*>(d);
+                uint32_t ntiles = uint32_t(list[mt].size() * tpb);
+                uint32_t S32 = uint32_t(S), cpb32 = uint32_t(cpb), tpb32 = uint32_t(tpb);
+                uint64_t bs64 = bs, rs64 = rs;
+                void* args[] = {&dl, &dp, &sbase, &bs64, &rs64, &S32, &cpb32, &tpb32, &ntiles};
+                const uint64_t wgs = std::min<uint64_t>((uint64_t(ntiles) + wpg - 1) / wpg, uint64_t(wg_cap));
+                HIP_TRY(hipLaunchKernel(fn, dim3(uint32_t(wgs)), dim3(uint32_t(wpg * kWave)), args, 0, stream));
+                char buf[96];
+                std::snprintf(buf, sizeof buf, "rs_mixed_kernel<K=%d,MT=%d>%s", K, mt, aligned ? "" : ",UA");
+                set_last_kernel(c, buf);
+            }
+        }
+        // the fallback: the uniform call's launch per run of consecutive blocks with equal masks
+        for (uint64_t b = 0; b < sn;) {
+            const uint32_t p = mb.pat[s0 + b];
+            uint64_t e = b + 1;
+            while (e < sn && mb.pat[s0 + e] == p) e++;
+            if (cls[p] == kFallback) {
+                uint8_t* rb = sbase + b * bs;
+                int rc = launch_plan(c, *plans[p], rb, rs, bs, rb, rs, bs, S, e - b, stream);
+                if (rc) return rc;
+            }
+            b = e;
+        }
+    }
+    return hip_status(hipGetLastError());
+}
+
+namespace {
+
+void write_status(const MixedBatch& mb, size_t nblocks, int32_t* status_out) {
+    if (!status_out) return;
+    for (size_t b = 0; b < nblocks; b++) status_out[b] = mb.key_status[mb.pat[b]];
+}
+
+// The host-memory call on reconstruct_host_impl's three decisions: page-locked shards in place,
+// small pageable calls through the page-locked staging, everything else uploaded in ~64 MiB
+// chunks of whole blocks over the three staging slots.  Only wanted rows of blocks with status OK
+// are written into the caller's memory.
+int mixed_host_impl(rsmi_ctx* c, uint8_t* shards, size_t block_stride, size_t S, size_t nblocks,
+                    const uint8_t* present, const uint8_t* required, int data_only, int32_t* status_out) {
+    if (!c || !shards || !present) return RSMI_ERR_INVALID_ARG;
+    if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
+    if (block_stride < size_t(c->n) * S) return RSMI_ERR_INVALID_ARG;
+    if (nblocks == 0) return RSMI_OK;
+    MixedBatch mb;
+    classify_mixed(c, nblocks, present, required, data_only, mb);
+    if (mb.too_few && !status_out) return RSMI_ERR_TOO_FEW_SHARDS;
+    if (!mb.work) {
+        write_status(mb, nblocks, status_out);
+        return RSMI_OK;
+    }
+    std::lock_guard<std::mutex> g(c->mu);
+    int rc = ensure_device(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = size_t(c->n), blk = n * S;
+    // the rows of block b the call moves: in, the present rows; out, the rows it rebuilt
+    auto each_row = [&](size_t b, char which, auto&& fn) {
+        const uint32_t p = mb.pat[b];
+        if (!mb.key_rows[p]) return;
+        for (size_t i = 0; i < n; i++)
+            if (mb.keys[p][i] == which) fn(i);
+    };
+    uint8_t* dev = c->opt_zero_copy ? host_alias(shards, (nblocks - 1) * block_stride + blk) : nullptr;
+    if (dev || nblocks * blk <= size_t(c->opt_small_bytes)) {
+        hipStream_t st = c->staging[0].stream;
+        uint8_t* hs = nullptr;
+        size_t dbs = block_stride;
+        if (!dev) {
+            hs = small_stage(c, nblocks * blk);
+            if (!hs) return RSMI_ERR_DEVICE;
+            for (size_t b = 0; b < nblocks; b++)
+                each_row(b, '1', [&](size_t i) { std::memcpy(hs + b * blk + i * S, shards + b * block_stride + i * S, S); });
+            dev = host_alias(hs, nblocks * blk);
+            dbs = blk;
+            if (!dev) return RSMI_ERR_DEVICE;
+        }
+        if ((rc = launch_mixed(c, mb, dev, S, dbs, S, 0, nblocks, st))) return rc;
+        HIP_TRY(hipStreamSynchronize(st));
+        if (hs)
+            for (size_t b = 0; b < nblocks; b++)
+                each_row(b, '2', [&](size_t i) { std::memcpy(shards + b * block_stride + i * S, hs + b * blk + i * S, S); });
+        write_status(mb, nblocks, status_out);
+        return RSMI_OK;
+    }
+    // Whole blocks go up linearly at pitch S (the kernels take that pitch as it is: the
+    // unaligned-window form, or the aligned one when S is a multiple of 16), so every row crosses
+    // PCIe on the way in, missing ones included; the rebuilt rows come back one copy each, behind
+    // the chunk's kernels on its slot's stream, before a later chunk's upload reuses the slot.
+    const size_t chunk = std::max<size_t>(1, (size_t(64) << 20) / blk);
+    const int ns = nblocks > chunk ? 3 : 1;
+    for (size_t b0 = 0, i = 0; b0 < nblocks; b0 += chunk, i++) {
+        Staging& st = c->staging[i % ns];
+        const size_t nb = std::min(chunk, nblocks - b0);
+        if ((rc = reserve(st.d_lin, st.lin_cap, nb * blk))) return rc;
+        const uint8_t* h = shards + b0 * block_stride;
+        if (block_stride == blk)
+            HIP_TRY(hipMemcpyAsync(st.d_lin, h, nb * blk, hipMemcpyHostToDevice, st.stream));
+        else
+            for (size_t b = 0; b < nb; b++)
+                HIP_TRY(hipMemcpyAsync(st.d_lin + b * blk, h + b * block_stride, blk, hipMemcpyHostToDevice, st.stream));
+        if ((rc = launch_mixed(c, mb, st.d_lin, S, blk, S, b0, nb, st.stream))) return rc;
+        for (size_t b = 0; b < nb; b++) {
+            hipError_t e = hipSuccess;
+            each_row(b0 + b, '2', [&](size_t r) {
+                if (e == hipSuccess)
+                    e = hipMemcpyAsync(shards + (b0 + b) * block_stride + r * S, st.d_lin + b * blk + r * S, S,
+                                       hipMemcpyDeviceToHost, st.stream);
+            });
+            HIP_TRY(e);
+        }
+    }
+    for (int s = 0; s < ns; s++) HIP_TRY(hipStreamSynchronize(c->staging[s].stream));
+    write_status(mb, nblocks, status_out);
+    return RSMI_OK;
+}
+
+}  // namespace
+
+}  // namespace impl
+}  // namespace rsmi
+
+extern "C" {
+
+int rsmi_reconstruct_mixed_classify(const rsmi_ctx* c, size_t nblocks, const uint8_t* present, const uint8_t* required,
+                                    int data_only, int32_t* status_out, uint8_t* rows_out, uint32_t* pattern_out,
+                                    size_t* npatterns_out) try {
+    if (!c || (nblocks && !present)) return RSMI_ERR_INVALID_ARG;
+    MixedBatch mb;
+    classify_mixed(c, nblocks, present, required, data_only, mb);
+    for (size_t b = 0; b < nblocks; b++) {
+        const uint32_t p = mb.pat[b];
+        if (status_out) status_out[b] = mb.key_status[p];
+        if (rows_out) rows_out[b] = mb.key_rows[p];
+        if (pattern_out) pattern_out[b] = p;
+    }
+    if (npatterns_out) *npatterns_out = mb.keys.size();
+    return RSMI_OK;
+} catch (...) {
+    return rsmi::impl::exception_status();
+}
+
+int rsmi_reconstruct_mixed_batch_dev(rsmi_ctx* c, uint8_t* d_shards, size_t shard_stride, size_t block_stride, size_t S,
+                                     size_t nblocks, const uint8_t* present, const uint8_t* required, int data_only,
+                                     int32_t* status_out, void* stream) try {
+    if (!c || !d_shards || !present) return RSMI_ERR_INVALID_ARG;
+    if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
+    if (shard_stride < S) return RSMI_ERR_INVALID_ARG;
+    if (nblocks == 0) return RSMI_OK;
+    MixedBatch mb;
+    classify_mixed(c, nblocks, present, required, data_only, mb);
+    if (mb.too_few && !status_out) return RSMI_ERR_TOO_FEW_SHARDS;
+    if (mb.work) {
+        std::lock_guard<std::mutex> g(c->mu);
+        int rc = ensure_device(c);
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(c->device));
+        rc = launch_mixed(c, mb, d_shards, shard_stride, block_stride, S, 0, nblocks, static_cast<hipStream_t>(stream));
+        if (rc) return rc;
+    }
+    write_status(mb, nblocks, status_out);
+    return RSMI_OK;
+} catch (...) {
+    return rsmi::impl::exception_status();
+}
+
+int rsmi_reconstruct_mixed_batch_host(rsmi_ctx* c, uint8_t* shards, size_t block_stride, size_t S, size_t nblocks,
+                                      const uint8_t* present, const uint8_t* required, int data_only,
+                                      int32_t* status_out) try {
+    return mixed_host_impl(c, shards, block_stride, S, nblocks, present, required, data_only, status_out);
+} catch (...) {
+    return rsmi::impl::exception_status();
+}
+
+}  // extern "C"

@@ -86,6 +86,13 @@ def lib() -> ctypes.CDLL:
         "rsmi_host_free": (None, [ctypes.c_void_p]),
         "rsmi_encode_batch_dev": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, u8p, c_size, c_size, c_size, c_size, ctypes.c_void_p]),
         "rsmi_reconstruct_batch_dev": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, c_size, c_size, u8p, ctypes.c_int, ctypes.c_void_p]),
+        "rsmi_reconstruct_mixed_batch_dev": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, c_size, c_size, u8p, u8p,
+                                                            ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+        "rsmi_reconstruct_mixed_batch_host": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, c_size, u8p, u8p,
+                                                             ctypes.c_int, ctypes.c_void_p]),
+        "rsmi_reconstruct_mixed_classify": (ctypes.c_int, [ctypes.c_void_p, c_size, u8p, u8p, ctypes.c_int,
+                                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                           ctypes.POINTER(c_size)]),
         "rsmi_verify_batch_dev": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, u8p, c_size, c_size, c_size, c_size,
                                                  ctypes.c_void_p, ctypes.c_void_p]),
         "rsmi_verify_batch_host": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, u8p, c_size, c_size, c_size,
@@ -445,6 +452,62 @@ class Codec:
         _check(lib().rsmi_reconstruct_batch_dev(self._h, d_shards, rs, bs, S, nblocks, ctypes.addressof(_buf(p)),
                                                 1 if data_only else 0, stream or None))
 
+    # -- mixed batches: a present (and required) mask per block (rsmi_reconstruct_mixed_*).  A mask
+    # argument is nblocks rows of k + m flags (nested sequences, bytes, or a numpy array) or the
+    # address of nblocks * (k + m) bytes; required may be None.
+    def _masks(self, masks, nblocks: int):
+        """(address or None, the object that keeps the bytes alive)."""
+        if masks is None:
+            return None, None
+        if isinstance(masks, int):
+            return masks, None
+        n = self.k + self.m
+        if hasattr(masks, "tobytes"):
+            flat = bytearray(masks.tobytes())
+        elif isinstance(masks, (bytes, bytearray)):
+            flat = bytearray(masks)
+        else:
+            flat = bytearray(1 if x else 0 for row in masks for x in row)
+        if len(flat) != nblocks * n:
+            raise RsmiError(ErrInvalidArg, "a mask needs nblocks * (k + m) flags")
+        keep = _buf(flat) if flat else None
+        return (ctypes.addressof(keep) if flat else None), keep
+
+    def reconstruct_mixed_batch_dev(self, d_shards: int, rs: int, bs: int, S: int, nblocks: int, present,
+                                    required=None, data_only: bool = False, stream: int = 0,
+                                    status: bool = True) -> Optional[List[int]]:
+        """rsmi_reconstruct_mixed_batch_dev.  status: take the per-block statuses (returned as a
+        list; blocks with too few rows present are skipped); without it such a block fails the
+        whole call with ErrTooFewShards before anything is launched."""
+        p, keep_p = self._masks(present, nblocks)
+        q, keep_q = self._masks(required, nblocks)
+        st = (ctypes.c_int32 * max(nblocks, 1))() if status else None
+        _check(lib().rsmi_reconstruct_mixed_batch_dev(self._h, d_shards, rs, bs, S, nblocks, p, q,
+                                                      1 if data_only else 0, st, stream or None))
+        return list(st)[:nblocks] if status else None
+
+    def reconstruct_mixed_batch_host_ptr(self, ptr: int, bs: int, S: int, nblocks: int, present, required=None,
+                                         data_only: bool = False, status: bool = True) -> Optional[List[int]]:
+        """rsmi_reconstruct_mixed_batch_host on nblocks blocks of host memory at ptr."""
+        p, keep_p = self._masks(present, nblocks)
+        q, keep_q = self._masks(required, nblocks)
+        st = (ctypes.c_int32 * max(nblocks, 1))() if status else None
+        _check(lib().rsmi_reconstruct_mixed_batch_host(self._h, ptr, bs, S, nblocks, p, q, 1 if data_only else 0, st))
+        return list(st)[:nblocks] if status else None
+
+    def reconstruct_mixed_classify(self, nblocks: int, present, required=None, data_only: bool = False):
+        """rsmi_reconstruct_mixed_classify, device-free: (statuses, rows written per block, the
+        blocks' pattern indices by first appearance, the number of patterns)."""
+        p, keep_p = self._masks(present, nblocks)
+        q, keep_q = self._masks(required, nblocks)
+        st = (ctypes.c_int32 * max(nblocks, 1))()
+        rows = (ctypes.c_uint8 * max(nblocks, 1))()
+        pat = (ctypes.c_uint32 * max(nblocks, 1))()
+        npat = ctypes.c_size_t(0)
+        _check(lib().rsmi_reconstruct_mixed_classify(self._h, nblocks, p, q, 1 if data_only else 0, st, rows, pat,
+                                                     ctypes.byref(npat)))
+        return list(st)[:nblocks], list(rows)[:nblocks], list(pat)[:nblocks], int(npat.value)
+
 
 class DeviceGroup:
     """Several GPUs from one process (rsmi_group_open): batches split into contiguous block
@@ -624,6 +687,49 @@ class Erasure:
         if is_zero == 0 or is_zero == len(data):
             return
         self._reconstruct(data, data_only=True)
+
+    def decode_data_blocks_many(self, blocks: List[List[Optional[bytes]]]) -> None:
+        """decode_data_blocks for many blocks at once, each with its own missing shards, through
+        one rsmi_reconstruct_mixed_batch_host call.  Every block passes decode_data_blocks' checks
+        first, in order (the isZero loop, the shard count, checkShards, nothing missing, fewer than
+        k shards present); when a block fails one, the first such block's sentinel is raised before
+        anything is decoded, and no list is changed.  Blocks that need decoding must share one
+        shard size (ErrShardSize at the first that differs).  The missing data shards of every
+        block are then filled in place, as decode_data_blocks fills them."""
+        k, n = self.data_blocks, self.data_blocks + self.parity_blocks
+        work = []  # (block index, present flags)
+        S = 0
+        for bi, data in enumerate(blocks):
+            if all(data) or len(data) == 1:  # decode_data_blocks' isZero short-circuit
+                continue
+            if len(data) != n:
+                raise RsmiError(ErrTooFewShards)
+            rc, s = check_shards([len(x) if x else 0 for x in data], nil_ok=True)
+            _check(rc)
+            present = [bool(x) for x in data]
+            if sum(present[:k]) == k:
+                continue
+            if sum(present) < k:
+                raise RsmiError(ErrTooFewShards)
+            if work and s != S:
+                raise RsmiError(ErrShardSize)
+            S = s
+            work.append((bi, present))
+        if not work:
+            return
+        flat = bytearray(len(work) * n * S)
+        for j, (bi, present) in enumerate(work):
+            for i, x in enumerate(blocks[bi]):
+                if x:
+                    flat[(j * n + i) * S:(j * n + i + 1) * S] = x
+        status = self.encoder().reconstruct_mixed_batch_host_ptr(
+            ctypes.addressof(_buf(flat)), n * S, S, len(work), [p for _, p in work], None, True)
+        for st in status:
+            _check(st)
+        for j, (bi, present) in enumerate(work):
+            for i in range(k):
+                if not present[i]:
+                    blocks[bi][i] = bytes(flat[(j * n + i) * S:(j * n + i + 1) * S])
 
     def decode_data_and_parity_blocks(self, data: List[Optional[bytes]]) -> None:
         """erasure.go:87-93 DecodeDataAndParityBlocks -> Reconstruct."""

@@ -37,8 +37,9 @@ extern "C" {
  * 5: the per-thread wait hook (rsmi_set_wait_hook, rsmi_run_wait_hook).  The Encoder.Verify entry
  * points (rsmi_verify, rsmi_verify_batch_host, rsmi_verify_batch_dev) joined version 5: additive;
  * so did the locate entry points (rsmi_locate, rsmi_locate_batch_host, rsmi_locate_batch_dev,
- * rsmi_locate_matrix) and the heal entry points (rsmi_heal, rsmi_heal_batch_host,
- * rsmi_heal_batch_dev). */
+ * rsmi_locate_matrix), the heal entry points (rsmi_heal, rsmi_heal_batch_host,
+ * rsmi_heal_batch_dev) and the mixed-batch reconstruct (rsmi_reconstruct_mixed_batch_dev,
+ * rsmi_reconstruct_mixed_batch_host, rsmi_reconstruct_mixed_classify). */
 #define RSMI_ABI_VERSION 5
 
 typedef struct rsmi_ctx rsmi_ctx;
@@ -162,6 +163,66 @@ int rsmi_reconstruct_batch_dev(rsmi_ctx* ctx, uint8_t* d_shards, size_t shard_st
 int rsmi_reconstruct_rows_batch_dev(rsmi_ctx* ctx, uint8_t* d_shards, size_t shard_stride, size_t block_stride,
                                     size_t S, size_t nblocks, const uint8_t* present, const uint8_t* required,
                                     void* stream);
+
+/* ------------------------------------------------------------------ mixed batches: a pattern per block */
+
+/* The reconstruct calls above take one erasure pattern for the whole batch, which fits a repair
+ * after one datanode is lost.  Checksum failures, slow or failed fetches and half-finished repairs
+ * give every block its own pattern; these calls rebuild such a batch in one go, with no sort of the
+ * blocks by pattern and no call per pattern.
+ *   Masks.  present and required hold nblocks x (k+m) bytes in HOST memory, block-major: byte
+ *   b*(k+m) + i is the flag of row i of block b.  They are read before the call returns: the caller
+ *   may free or overwrite them at once, also after the stream-ordered _dev call.  required == NULL:
+ *   the rows to rebuild in a block are its missing data rows (data_only != 0) or all its missing
+ *   rows (data_only == 0), as rsmi_reconstruct_batch_*.  required != NULL: per block the rule of
+ *   rsmi_reconstruct_rows_batch_* (the missing rows that are flagged), data_only is ignored.
+ *   What is written.  In every block whose status is RSMI_OK, bytes [0, S) of each wanted missing
+ *   row are written, and they are the bytes rsmi_reconstruct_rows_batch_dev writes for that block
+ *   alone under that block's masks: the survivors are the first k present rows, data rows come from
+ *   the inverse of their sub-matrix, missing parity rows from M[i] x inverse.  Nothing else is
+ *   written: no present row, no missing row that is not wanted, no byte at or past S of any row, no
+ *   byte of a gap, no byte of a block that has nothing to rebuild, no byte of a block with fewer
+ *   than k rows present.  The layout contract holds: padding may be read and is never written.
+ *   Status.  status_out (host memory, nblocks int32, may be NULL) receives per block RSMI_OK or
+ *   RSMI_ERR_TOO_FEW_SHARDS (a wanted row is missing and fewer than k rows are present; a block
+ *   that has nothing to rebuild is RSMI_OK whatever it has present, as upstream).  With status_out
+ *   given the call rebuilds the other blocks and returns RSMI_OK; with status_out == NULL a batch
+ *   with such a block returns RSMI_ERR_TOO_FEW_SHARDS before any launch and writes nothing, the
+ *   whole-batch behaviour of the calls above.  status_out is written only when the call returns
+ *   RSMI_OK.
+ *   Arguments.  The checks, their order and their statuses are those of rsmi_reconstruct_batch_dev
+ *   / _host: a NULL ctx, shards or present -> RSMI_ERR_INVALID_ARG; S == 0 ->
+ *   RSMI_ERR_SHARD_NO_DATA; a shard stride below S, or (host) a block stride below (k+m)*S ->
+ *   RSMI_ERR_INVALID_ARG; nblocks == 0 -> RSMI_OK.  They come before any device access, as does the
+ *   classing of the masks: a batch with nothing to rebuild returns RSMI_OK without a device, any
+ *   other on a host without a GPU RSMI_ERR_NO_DEVICE, with nothing written.
+ * The calls are joined to ABI version 5 (additive); none of them takes or clears the per-thread
+ * wait hook. */
+
+/* Device-resident, in place: row i of block b at d_shards + b*block_stride + i*shard_stride, fast
+ * path alignment as rsmi_encode_batch_dev.  Stream-ordered, no sync: the blocks' classes travel to
+ * per-stream scratch on the same stream (growing it, or starting it over once it is used up,
+ * waits for that stream once). */
+int rsmi_reconstruct_mixed_batch_dev(rsmi_ctx* ctx, uint8_t* d_shards, size_t shard_stride, size_t block_stride,
+                                     size_t S, size_t nblocks, const uint8_t* present, const uint8_t* required,
+                                     int data_only, int32_t* status_out, void* stream);
+
+/* Host memory: block b at shards + b*block_stride holds k+m rows of S bytes.  Page-locked shards
+ * (rsmi_host_alloc) are rebuilt where they lie; small pageable calls are staged by CPU copies;
+ * larger ones are uploaded in chunks of whole blocks, and only the rebuilt rows come back. */
+int rsmi_reconstruct_mixed_batch_host(rsmi_ctx* ctx, uint8_t* shards, size_t block_stride, size_t S, size_t nblocks,
+                                      const uint8_t* present, const uint8_t* required, int data_only,
+                                      int32_t* status_out);
+
+/* Host-only, works without a GPU, like rsmi_decode_matrix: what the two calls above will do with
+ * these masks.  Every output may be NULL.  status_out[b]: as above.  rows_out[b]: the rows the call
+ * writes in block b, 0..m (0 for a block with too few rows present).  pattern_out[b]: the index of
+ * the block's distinct (present, want) pair, numbered by first appearance, where present is taken
+ * as 0 / 1 per row and want is "this row is missing and to be rebuilt"; blocks with equal indices
+ * share one decode matrix and one set of kernel tables.  *npatterns_out: the number of pairs. */
+int rsmi_reconstruct_mixed_classify(const rsmi_ctx* ctx, size_t nblocks, const uint8_t* present,
+                                    const uint8_t* required, int data_only, int32_t* status_out, uint8_t* rows_out,
+                                    uint32_t* pattern_out, size_t* npatterns_out);
 
 /* ------------------------------------------------------------------ Encoder.Verify */
 
