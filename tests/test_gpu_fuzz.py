@@ -464,3 +464,240 @@ def test_random_stripe_checks(seed):
     _STRIPE.pop(seed, None)
     if seed == STRIPE_CASES - 1:
         print("\nstripe fuzz: heal calls run and asserted by label, per family:", dict(_STRIPE_SEEN["heal"]))
+
+
+# ---------------------------------------------------------------- the mixed-batch reconstruct
+# Seeded random mixed batches: every block draws its own loss count (0 .. m + 1) and rows, the
+# batch draws shape, size, layout (test_mixed_layouts' one side through _stripe_side), required
+# masks, data_only, waves_per_cu and the entry point.  Statuses and the whole buffer against
+# test_mixed_reconstruct.definition, the label against test_mixed_layouts.expected_label on the
+# pointer the call really got.
+MIXED_CASES = 48
+MIXED_SEED_BASE = 88000
+MIXED_ENTRIES = ["dev", "dev-side-stream", "host-locked", "host-pageable", "host-upload"]
+MIXED_ENTRY_P = [0.36, 0.28, 0.12, 0.12, 0.12]
+MIXED_LAYOUT_P = [0.22, 0.22, 0.46, 0.1]    # over LAYOUTS: "odd" is the only UA layout with rs > S
+MIXED_S_P = [0.08, 0.08, 0.08, 0.14, 0.3, 0.32]   # rows of several tiles: UA grids of 8 workgroups and more
+MIXED_M_P = [1, 1, 1, 1, 1, 2, 2, 2, 3, 3, 3, 2, 2, 2, 2]   # over STRIPE_MS, before normalising
+_MIXED = {}
+_MIXED_DRAW = {}
+
+
+def _mixed_draw(seed):
+    """The parameters of a case: cheap, nothing of the oracle's."""
+    if seed in _MIXED_DRAW:
+        return _MIXED_DRAW[seed]
+    from test_layout_contract import GUARD, Side
+    from test_mixed_layouts import expected_form
+
+    r = np.random.default_rng(MIXED_SEED_BASE + seed)
+    k = int(r.choice(STRIPE_KS))
+    m = int(r.choice(STRIPE_MS, p=np.array(MIXED_M_P) / float(sum(MIXED_M_P))))
+    n = k + m
+    S = int(r.choice([16, 17, 31, int(r.integers(1, 16)), int(r.integers(1, 5000)), int(r.integers(5000, 20001))],
+                     p=MIXED_S_P))
+    nb = int(r.integers(1, 65))
+    entry = str(r.choice(MIXED_ENTRIES, p=MIXED_ENTRY_P))
+    lay = str(r.choice(LAYOUTS, p=MIXED_LAYOUT_P))
+    wpc1 = bool(r.integers(0, 4) == 0)
+    # waves_per_cu = 1 leaves a 256-CU device 256 waves per launch: two such cases in three draw
+    # long rows, many blocks and mostly one lost row, so that a class has more tiles than that and
+    # the waves walk on (nb stays within 1..64)
+    walk = wpc1 and bool(r.random() < 2.0 / 3)
+    if walk:
+        S, nb = int(r.integers(16000, 20001)), int(r.integers(48, 65))
+    data_only = bool(r.random() < 0.35)
+    present = np.ones((nb, n), dtype=bool)
+    for b in range(nb):
+        nl = 1 if walk and r.random() < 0.6 else int(r.integers(0, m + 2))
+        present[b, r.choice(n, size=nl, replace=False)] = False
+    required = (r.random(size=(nb, n)) < 0.6) if r.random() < 0.35 else None
+    if entry.startswith("dev"):
+        side = _stripe_side(lay, "x", n, S, nb, 0)
+    else:  # host memory: rows at pitch S, a drawn block stride
+        side = Side("x", 0, S, n * S + int(r.choice([0, int(r.integers(1, 40))])))
+    # the layout launch_mixed sees: the caller's on the device and in page-locked memory, whole
+    # blocks at pitch S in the staging of the other two
+    seen = side if entry in ("dev", "dev-side-stream", "host-locked") else Side("x", 0, S, n * S)
+    form = expected_form(GUARD + seen.off, seen.rs, seen.bs, S)   # from a 16-byte-aligned allocation
+    d = dict(k=k, m=m, S=S, nb=nb, entry=entry, lay=lay, wpc1=wpc1, data_only=data_only, present=present,
+             required=required, side=side, seen=seen, form=form, data_seed=int(r.integers(0, 2 ** 31)))
+    _MIXED_DRAW[seed] = d
+    return d
+
+
+def _mixed_rows(d):
+    from test_mixed_layouts import rows_rebuilt
+    from test_mixed_reconstruct import wanted
+
+    W = wanted(d["k"], d["present"], d["required"], d["data_only"])
+    return W, rows_rebuilt(d["k"], d["present"], W)
+
+
+def _mixed_case(seed):
+    """The draw, the shards and the definition's answers, computed once per seed."""
+    if seed in _MIXED:
+        return _MIXED[seed]
+    from test_mixed_reconstruct import definition, junk_unused_survivor, stored
+
+    d = dict(_mixed_draw(seed))
+    k, m, S, nb = d["k"], d["m"], d["S"], d["nb"]
+    r = np.random.default_rng(d["data_seed"])
+    data = r.integers(0, 256, size=(nb, k, S), dtype=np.uint8)
+    sh = stored(np.concatenate([data, orc.encode_fast(k, m, data, threads=4)], axis=1), d["present"])
+    junk_unused_survivor(k, sh, d["present"])
+    W, rows = _mixed_rows(d)
+    status, image = definition(k, m, sh, d["present"], W)
+    d.update(sh=sh, W=W, rows=rows, status=status, image=image)
+    _MIXED[seed] = d
+    return d
+
+
+def _mixed_grids(d, rows):
+    """The workgroups of each class launch of an uncapped call, as launch_mixed sizes them."""
+    cpb = (d["S"] + 15) // 16
+    tpb = (cpb + 63) // 64
+    return [(int((rows == mt).sum()) * tpb + 3) // 4 for mt in (1, 2, 3, 4) if (rows == mt).any()]
+
+
+def test_mixed_generator_coverage():
+    """The committed seed range reaches what the fuzz is there for (conditions on the generator,
+    not measurements)."""
+    import collections
+    import os
+
+    from test_kernel_matrix import KS
+    from test_mixed_reconstruct import MIXED_CPP
+
+    with open(MIXED_CPP) as f:
+        src = " ".join(f.read().split())
+    with open(os.path.join(os.path.dirname(MIXED_CPP), "rs_plan.hpp")) as f:
+        plan = f.read()
+    assert "const uint64_t cpb = (S + 15) / 16;" in src
+    assert "const uint64_t tpb = (cpb + uint64_t(kWave) - 1) / uint64_t(kWave);" in src
+    assert "constexpr int wpg = kFastWG / kWave;" in src
+    assert "uint32_t ntiles = uint32_t(list[mt].size() * tpb);" in src
+    assert ("const uint64_t wgs = std::min<uint64_t>((uint64_t(ntiles) + wpg - 1) / wpg, uint64_t(wg_cap));") in src
+    assert "constexpr int kWave = 64;" in plan and "constexpr int kWG = 256;" in plan
+    assert "constexpr int kFastWG = kWG;" in plan
+
+    t = collections.Counter()
+    class_blocks, class_cases = collections.Counter(), collections.Counter()
+    for seed in range(MIXED_CASES):
+        d = _mixed_draw(seed)
+        k, m, S, nb, side, form = d["k"], d["m"], d["S"], d["nb"], d["side"], d["form"]
+        n = k + m
+        assert 1 <= nb <= 64 and side.rs >= S and side.bs >= n * side.rs
+        W, rows = _mixed_rows(d)
+        has_class = form != "generic" and k in KS
+        work = rows > 0
+        fast = work & (rows <= 4) & has_class
+        for mt in (1, 2, 3, 4):
+            cnt = int((fast & (rows == mt)).sum())
+            class_blocks[mt] += cnt
+            class_cases[mt] += cnt > 0
+        t["three classes"] += len(set(rows[fast].tolist())) >= 3
+        t["fallback: more than 4 rows"] += bool(has_class and (rows > 4).any())
+        t["fallback: K without a kernel"] += bool(k not in KS and work.any())
+        t["fallback: neither form"] += bool(form == "generic" and work.any())
+        assert form != "generic" or S < 16
+        t["fast and fallback"] += bool(fast.any() and (work & ~fast).any())
+        few = (d["present"].sum(axis=1) < k) & W.any(axis=1)
+        t["too few"] += bool(few.any())
+        t["no work"] += bool((~W.any(axis=1)).any())
+        t["required"] += d["required"] is not None
+        t["data_only"] += d["data_only"]
+        t["aligned"] += bool(form == "aligned" and work.any())
+        t["UA, rs > S"] += bool(form == "ua" and d["seen"].rs > S and work.any())
+        t["waves_per_cu = 1"] += d["wpc1"]
+        # the cap of waves_per_cu = 1 on 256 CUs is 64 workgroups: a class launch with more tiles
+        # than their 256 waves is walked
+        walked = any(g > 64 for g in _mixed_grids(d, np.where(fast, rows, 0)))
+        t["waves_per_cu = 1, walked"] += bool(d["wpc1"] and walked)
+        t[d["entry"]] += 1
+        if form == "ua" and fast.any() and not d["wpc1"]:
+            grids = _mixed_grids(d, np.where(fast, rows, 0))
+            t["UA grid % 8 == 0"] += any(g % 8 == 0 for g in grids)
+            t["UA grid % 8 != 0"] += any(g % 8 != 0 for g in grids)
+    print("\nmixed fuzz generator:", dict(t), "class blocks", dict(class_blocks), "class cases", dict(class_cases))
+    for mt in (1, 2, 3, 4):
+        assert class_blocks[mt] >= 10 and class_cases[mt] >= 5, (mt, dict(class_blocks), dict(class_cases))
+    assert t["three classes"] >= 15, dict(t)
+    for cause in ("more than 4 rows", "K without a kernel", "neither form"):
+        assert t["fallback: " + cause] >= 3, (cause, dict(t))
+    assert t["fast and fallback"] >= 3, dict(t)
+    assert t["too few"] >= 8 and t["no work"] >= 8, dict(t)
+    assert t["required"] >= 12 and t["data_only"] >= 12, dict(t)
+    assert t["aligned"] >= 10 and t["UA, rs > S"] >= 10, dict(t)
+    for entry in MIXED_ENTRIES:
+        assert t[entry] >= 3, (entry, dict(t))
+    assert t["UA grid % 8 == 0"] >= 3 and t["UA grid % 8 != 0"] >= 3, dict(t)
+    assert t["waves_per_cu = 1, walked"] >= 3, dict(t)
+    assert "if (c->opt_waves_per_cu > 0) wg_cap = std::max(1L, long(c->num_cu) * c->opt_waves_per_cu / wpg);" in src
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", range(MIXED_CASES))
+def test_random_mixed_batches(seed):
+    """One mixed call per case on a context of its own: the statuses, the whole buffer (guards,
+    padding and gaps included) and the label, which is "" where no block has work."""
+    import ctypes
+
+    import torch
+
+    from test_layout_contract import FILL_DATA, GUARD, put
+    from test_mixed_layouts import buf_size, compare, expected_form, expected_label
+    from test_mixed_reconstruct import u8
+
+    d = _mixed_case(seed)
+    k, m, S, nb, side, entry = d["k"], d["m"], d["S"], d["nb"], d["side"], d["entry"]
+    n = k + m
+    ctx = (seed, k, m, S, nb, entry, d["lay"], tuple(side), d["wpc1"], d["data_only"], d["required"] is not None)
+    size = buf_size(side, n, S, nb)
+    host = np.full(size, FILL_DATA, dtype=np.uint8)
+    put({"x": host}, side, d["sh"])
+    want = host.copy()
+    put({"x": want}, side, d["image"])
+    present, required = u8(d["present"]), None if d["required"] is None else u8(d["required"])
+    L = rsmi.lib()
+    pinned = None
+    try:
+        with rsmi.Codec(k, m) as c:
+            if d["wpc1"]:
+                c.set_option("waves_per_cu", 1)
+            if entry.startswith("dev"):
+                t = torch.from_numpy(host).cuda()
+                assert t.data_ptr() % 16 == 0
+                ptr = t.data_ptr() + GUARD + side.off
+                form = expected_form(ptr, side.rs, side.bs, S)
+                if entry == "dev":
+                    got = c.reconstruct_mixed_batch_dev(ptr, side.rs, side.bs, S, nb, present, required, d["data_only"],
+                                                        torch.cuda.current_stream().cuda_stream)
+                else:
+                    s = torch.cuda.Stream()
+                    s.wait_stream(torch.cuda.current_stream())
+                    got = c.reconstruct_mixed_batch_dev(ptr, side.rs, side.bs, S, nb, present, required, d["data_only"],
+                                                        s.cuda_stream)
+                torch.cuda.synchronize()
+                out = t.cpu().numpy()
+            else:
+                if entry == "host-locked":
+                    pinned = L.rsmi_host_alloc(size)
+                    assert pinned and pinned % 16 == 0
+                    out = np.ctypeslib.as_array((ctypes.c_uint8 * size).from_address(pinned))
+                    out[:] = host
+                    form = expected_form(pinned + GUARD, S, side.bs, S)
+                else:
+                    out = host.copy()
+                    form = expected_form(0, S, n * S, S)
+                    if entry == "host-upload":
+                        c.set_option("small_call_bytes", 0)
+                got = c.reconstruct_mixed_batch_host_ptr(out.ctypes.data + GUARD, side.bs, S, nb, present, required,
+                                                         d["data_only"])
+                out = out.copy()
+            assert form == d["form"], ctx
+            compare(got, out, c.last_kernel(), d["status"], want, expected_label(k, d["rows"], form) or "", ctx)
+    finally:
+        if pinned:
+            L.rsmi_host_free(pinned)
+    _MIXED.pop(seed, None)

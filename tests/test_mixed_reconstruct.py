@@ -17,6 +17,9 @@ waves hold tiles of different blocks, patterns and (through the class lists) pos
   8  equality with rsmi_reconstruct_rows_batch_dev; offsets past 4 GiB
   9  host entry: page-locked in place, small pageable, four chunks over the three slots
  10  no side effects on the other calls of the context; Erasure.decode_data_blocks_many
+ 11  the segment seam of launch_mixed: 2^22 + 5 blocks, fast classes and fallback runs across it
+ 12  past 32 caller streams: the scratch of every stream is freed on the way, twice
+ 13  host entry: three chunks with gaps between the blocks and per-block required masks
 """
 import ctypes
 import itertools
@@ -37,6 +40,8 @@ MISSING = 0x5C     # what a missing row holds before the call
 POISON = 0x5EED
 TOO_FEW = 2
 SIZES = [16, 1000, 1030, 3000, 5121]
+SEAM = 1 << 22         # blocks per segment of launch_mixed (leg 0 pins it)
+PAST_STREAMS = 40      # mixed_scratch() evicts once it keeps 32 streams (leg 0 pins it)
 
 
 @pytest.fixture(scope="module")
@@ -163,6 +168,14 @@ def test_chunk_rule_matches_source():
     assert src.count("Staging& st = c->staging[i % ns];") == 1
     assert re.findall(r"map\.size\(\)\s*>=\s*(\d+)", src) == ["32"]
     assert "size_t(1) << 20" in src  # the scratch's first size, which leg 6 outgrows
+    kept = int(re.findall(r"map\.size\(\)\s*>=\s*(\d+)", src)[0])
+    assert PAST_STREAMS == 40 > kept  # leg 12 stays beyond the eviction threshold
+    # leg 11: a segment of launch_mixed is at most 2^22 blocks
+    assert src.count("uint64_t(1) << 22") == 1 and SEAM == 1 << 22
+    assert ("const uint64_t seg = std::min<uint64_t>(std::max<uint64_t>(1, (uint64_t(1) << 31) / tpb), "
+            "uint64_t(1) << 22);") in " ".join(src.split())
+    assert "uint8_t* sbase = base + (s0 - b0) * bs;" in src
+    assert "list[cls[p]].push_back(MixedEntry{uint32_t(b), p});" in src
 
 
 # ---------------------------------------------------------------- 1: RS(4,2), every pattern in one call
@@ -657,3 +670,230 @@ def test_decode_data_blocks_many(gpu):
     one[1][0] = None
     e.decode_data_blocks(one[1])
     assert one[1] == shards[1]
+
+
+# ---------------------------------------------------------------- 11: the segment seam
+def seam_period():
+    """13 blocks of RS(2,2): the 4 one-lost and the 6 two-lost patterns with the classes
+    alternating, an intact block, a three-lost (too few) block and one two-lost pattern again.
+    13 does not divide 2^22, so the seam cuts the period."""
+    one = [(i,) for i in range(4)]
+    two = list(itertools.combinations(range(4), 2))
+    out = [two[0], one[0], two[1], one[1], (), two[2], one[2], two[3], (0, 1, 2), one[3], two[4], two[5], two[2]]
+    assert len(out) == 13 and len(set(out)) == 12 and SEAM % 13 != 0
+    return out
+
+
+def tiled_blocks(per_period, nb):
+    """per_period[b % period] for b in range(nb), along the first axis."""
+    p = per_period.shape[0]
+    return np.tile(per_period, (-(-nb // p),) + (1,) * (per_period.ndim - 1))[:nb]
+
+
+def seam_run(torch, c, off, rs, bs, S, sh, present, want_status, image, label, ctx):
+    """One call over nb = sh.shape[0] blocks at pitch rs, block stride bs, off bytes behind a
+    256-byte-aligned base, 64 guard bytes behind the last block: statuses, label, whole buffer."""
+    nb, n = sh.shape[0], sh.shape[1]
+
+    def render(rows):
+        buf = np.full(off + nb * bs + 64, GAP, dtype=np.uint8)
+        np.lib.stride_tricks.as_strided(buf[off:], shape=(nb, n, S), strides=(bs, rs, 1))[:] = rows
+        return buf
+
+    d = torch.from_numpy(render(sh)).cuda()
+    assert d.data_ptr() % 256 == 0
+    got = c.reconstruct_mixed_batch_dev(d.data_ptr() + off, rs, bs, S, nb, u8(present), None, False,
+                                        torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert c.last_kernel() == label, (ctx, c.last_kernel(), label)
+    assert np.array_equal(np.asarray(got, dtype=np.int32), want_status), ctx
+    out = d.cpu().numpy()
+    del d
+    same_bytes(out, render(image), ctx)
+
+
+@pytest.mark.gpu
+def test_segment_seam_fast_classes(gpu):
+    """2^22 + 5 blocks of RS(2,2), S = 16, rows at pitch 16: two segments, the second of 5 blocks.
+    Its base is sbase, its entries' blk count from the seam, its lists are the call's second
+    request to the stream's scratch.  The image is the period's definition, tiled."""
+    from test_mixed_layouts import expected_label, rows_rebuilt
+
+    torch, rsmi = gpu
+    k, m, S, nb = 2, 2, 16, SEAM + 5
+    period = seam_period()
+    P = present_of(4, period)
+    base = stored(stripes(k, m, S, 13), P)
+    W = wanted(k, P, None, False)
+    status, image = definition(k, m, base, P, W)
+    assert sorted(set(status)) == [0, TOO_FEW]
+    rows = tiled_blocks(rows_rebuilt(k, P, W), nb)
+    seam = [period[b % 13] for b in range(SEAM - 2, SEAM + 3)]
+    assert len(set(seam)) >= 3 and {1, 2} <= set(rows[SEAM - 2:SEAM + 3].tolist())
+    assert {1, 2} <= set(rows[SEAM:].tolist())
+    label = expected_label(k, rows, "aligned")
+    assert label == mixed_label(2, 2, True)
+    try:
+        with rsmi.Codec(k, m) as c:
+            seam_run(torch, c, 64, S, 4 * S, S, tiled_blocks(base, nb), tiled_blocks(P, nb),
+                     tiled_blocks(np.asarray(status, dtype=np.int32), nb), tiled_blocks(image, nb), label,
+                     "fast classes")
+    finally:
+        torch.cuda.empty_cache()
+
+
+@pytest.mark.gpu
+def test_segment_seam_cuts_a_fallback_run(gpu):
+    """RS(2,2), S = 8, rows at pitch 8 from an odd base: neither form, every block takes
+    launch_plan.  One pattern everywhere except blocks [2^22 - 1, 2^22 + 1), a run that the seam
+    cuts into two launches, and the batch's first block."""
+    from test_mixed_layouts import expected_label, rows_rebuilt
+
+    torch, rsmi = gpu
+    k, m, S, nb = 2, 2, 8, SEAM + 5
+    pats = [(0,), (1, 3), (0, 1)]
+    pid = np.zeros(nb, dtype=np.intp)
+    pid[SEAM - 1:SEAM + 1] = 1
+    pid[0] = 2
+    full = stripes(k, m, S, 13)
+    sh3, img3, rows3 = [], [], []
+    for lost in pats:
+        P = present_of(4, [lost] * 13)
+        sh = stored(full, P)
+        W = wanted(k, P, None, False)
+        status, image = definition(k, m, sh, P, W)
+        assert status == [0] * 13
+        sh3.append(sh)
+        img3.append(image)
+        rows3.append(rows_rebuilt(k, P, W)[0])
+    at = np.arange(nb) % 13
+    present = present_of(4, pats)[pid]
+    rows = np.asarray(rows3)[pid]
+    label = expected_label(k, rows, "generic")
+    assert label == generic_label(2, 1) and rows[SEAM] == 2
+    try:
+        with rsmi.Codec(k, m) as c:
+            seam_run(torch, c, 65, S, 4 * S, S, np.stack(sh3)[pid, at], present, np.zeros(nb, dtype=np.int32),
+                     np.stack(img3)[pid, at], label, "fallback run")
+    finally:
+        torch.cuda.empty_cache()
+
+
+# ---------------------------------------------------------------- 12: past 32 caller streams
+@pytest.mark.gpu
+def test_past_32_caller_streams(gpu):
+    """One Codec(10, 4), one mixed call on each of 40 distinct streams (collected as
+    test_stream_order's leg E collects them), then the same over the streams in reverse, with no
+    host sync between the calls: mixed_scratch() drains the device and frees every stream's lists
+    and their page-locked mirror on the way, twice.  No gate: a closed gate would never open
+    behind the eviction's hipDeviceSynchronize.  All 80 buffers and statuses against the
+    definition."""
+    from test_stream_order import _hip_runtime
+
+    torch, rsmi = gpu
+    k, m, nb = 10, 4, 24
+    streams, seen = [], set()
+
+    def add(s):
+        if s.cuda_stream not in seen:
+            seen.add(s.cuda_stream)
+            streams.append(s)
+
+    add(torch.cuda.current_stream())
+    add(torch.cuda.ExternalStream(0))
+    for prio in (0, -1):
+        for _ in range(64):
+            add(torch.cuda.Stream(priority=prio))
+    hip, own = None, []
+    try:
+        if len(streams) < PAST_STREAMS:
+            hip = _hip_runtime()
+            hip.hipStreamCreateWithFlags.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint]
+            hip.hipStreamDestroy.argtypes = [ctypes.c_void_p]
+            while len(streams) < PAST_STREAMS:
+                h = ctypes.c_void_p()
+                assert hip.hipStreamCreateWithFlags(ctypes.byref(h), 1) == 0  # hipStreamNonBlocking
+                own.append(h)
+                add(torch.cuda.ExternalStream(h.value))
+        handles = [s.cuda_stream for s in streams[:PAST_STREAMS]]
+        assert len(set(handles)) == PAST_STREAMS > 32 and 0 in handles
+        variants = [(1030, True), (1030, False), (3000, True)]
+        calls = []
+        for j, i in enumerate(list(range(PAST_STREAMS)) + list(reversed(range(PAST_STREAMS)))):
+            S, aligned = variants[i % 3]
+            lay = layout(rsmi, k, m, S, nb, aligned)
+            present = present_of(14, rs104_losses(nb, 1200 + j))
+            sh = stored(stripes(k, m, S, nb), present)
+            status, image = definition(k, m, sh, present, wanted(k, present, None, False))
+            host = lay.fill(sh)
+            expect = host.copy()
+            lay.rows(expect)[:] = image
+            d = torch.from_numpy(host).cuda()
+            assert d.data_ptr() % 256 == 0
+            calls.append((handles[i], lay, present, status, expect, d))
+        assert len({tuple(map(tuple, c_[2])) for c_ in calls}) == len(calls)
+        torch.cuda.synchronize()
+        with rsmi.Codec(k, m) as c:
+            got = [c.reconstruct_mixed_batch_dev(d.data_ptr() + lay.off, lay.rs, lay.bs, lay.S, nb, u8(present), None,
+                                                 False, h)
+                   for h, lay, present, _, _, d in calls]
+            torch.cuda.synchronize()
+            assert c.last_kernel() == mixed_label(10, 4, calls[-1][1].aligned)
+        for j, (h, lay, present, status, expect, d) in enumerate(calls):
+            assert got[j] == status, j
+            same_bytes(d.cpu().numpy(), expect, ("call", j, lay.S, lay.aligned))
+    finally:
+        torch.cuda.synchronize()
+        for h in own:
+            hip.hipStreamDestroy(h)
+
+
+# ---------------------------------------------------------------- 13: the host upload, strided, with required
+@pytest.mark.gpu
+def test_host_upload_strided_with_required(gpu):
+    """Pageable shards with 5 bytes between the blocks, three chunks over the three staging slots
+    (the per-block upload branch), a seeded required mask per block, a too-few block in the last
+    chunk.  The whole buffer is compared: rebuilt rows are the stripe's own, everything else (the
+    gap bytes' sentinel included) comes back unchanged; blocks next to every seam and every 97th
+    are also compared with the oracle under their masks."""
+    torch, rsmi = gpu
+    k, m, S = 4, 2, 2049
+    n = k + m
+    ch = host_chunk_blocks(n, S)
+    nb = 2 * ch + 3
+    bs = n * S + 5
+    assert -(-nb // ch) == 3 and nb * n * S > 2 << 20
+    sample = sorted({0, nb - 1, nb - 2} | set(range(0, nb, 97)) |
+                    {b for s in range(ch, nb, ch) for b in (s - 2, s - 1, s, s + 1)})
+    pats = [lost for lost in rs42_losses() if len(lost) <= m]
+    present = present_of(n, [pats[(b * 7 + b // ch) % 22] for b in range(nb)])
+    present[nb - 2] = [True, False, False, False, True, True]  # too few, in the last chunk
+    required = np.random.default_rng(1300).integers(0, 2, size=(nb, n)).astype(bool)
+    required[nb - 2] = True
+    W = wanted(k, present, required, False)
+    assert (required & present).any() and (~required & ~present).any()
+    assert {0, 1, 2} <= set(W.sum(axis=1).tolist())
+    want_status = np.zeros(nb, dtype=np.int32)
+    want_status[nb - 2] = TOO_FEW
+    Wok = W.copy()
+    Wok[nb - 2] = False
+    base = stripes(k, m, S, 64)
+    buf = np.full(nb * bs + 7, GAP, dtype=np.uint8)
+    rows = np.lib.stride_tricks.as_strided(buf, shape=(nb, n, S), strides=(bs, S, 1))
+    for b0 in range(0, nb, 64):
+        rows[b0:b0 + 64] = base[:min(64, nb - b0)]
+    expect = buf.copy()
+    erows = np.lib.stride_tricks.as_strided(expect, shape=(nb, n, S), strides=(bs, S, 1))
+    rows[~present] = MISSING
+    erows[~present & ~Wok] = MISSING
+    before = rows[sample]
+    with rsmi.Codec(k, m) as c:
+        got = c.reconstruct_mixed_batch_host_ptr(buf.ctypes.data, bs, S, nb, u8(present), u8(required), False)
+        # every chunk is a launch_mixed of its own, on rows at pitch S: the label is the last chunk's
+        last = Wok[2 * ch:].sum(axis=1)
+        assert last.any() and c.last_kernel() == mixed_label(4, int(last.max()), False)
+    assert np.array_equal(np.asarray(got, dtype=np.int32), want_status)
+    status, image = definition(k, m, before, present[sample], W[sample])
+    assert status == want_status[sample].tolist()
+    same_bytes(rows[sample].reshape(-1), image.reshape(-1), "sampled blocks")
+    same_bytes(buf, expect, "the whole buffer")
