@@ -201,6 +201,25 @@ struct HealKernelTable {
 const HealKernelTable& heal_kernels();
 void* heal_rows_kernel();
 
+// rsmi_locate_pair (rs_pair_kernels.hip): rs_locate_pair_kernel per (K, MT = m), the K of
+// rs_locate_kernel with m = 3..4 (m <= 2 names no pair), aligned and unaligned-window layouts; the
+// verdict kernel that ends every pair call, and the byte-granular kernel of the fallback
+struct PairKernelTable {
+    void* fn[17][kMaxMT + 1];
+    void* ua[17][kMaxMT + 1];
+};
+const PairKernelTable& pair_kernels();
+void* pair_verdict_kernel();
+void* pair_rows_kernel();
+// The pair tests of a tile kernel (rs_pair_tile.hpp), in the order of plan "P" (rsmi_pair.cpp):
+// per data shard c the test of {c, parity 0}, then of {c, d} for d = c + 1 .. K - 1; each takes
+// m - 2 coefficients, four to a column block of the plan.
+constexpr int pair_tests(int K) { return K + K * (K - 1) / 2; }
+constexpr int pair_blocks(int K, int MT) { return (pair_tests(K) * (MT - 2) + 3) / 4; }
+// bit p of a block's pair words: the lexicographic index of (x, y), x < y < n
+constexpr int pair_bit(int n, int x, int y) { return x * n - x * (x + 1) / 2 + (y - x - 1); }
+constexpr int pair_words(int n) { return (n * (n - 1) / 2 + 31) / 32; }
+
 // rsmi_reconstruct_mixed_batch_* (rs_mixed_kernels.hip): rs_mixed_kernel per (K, MT), the K of
 // the verify kernels, aligned and unaligned-window layouts (null when the shape has none).  A
 // launch codes the tiles of one class of blocks: entry e of its list names the block and, through

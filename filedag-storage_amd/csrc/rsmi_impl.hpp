@@ -9,9 +9,11 @@
 //   rsmi_locate.cpp    rsmi_locate: the shard that breaks a stripe, from Verify's syndromes
 //   rsmi_heal.cpp      rsmi_heal: locate, then the named shard rewritten on the same stream
 //   rsmi_mixed.cpp     rsmi_reconstruct_mixed_*: a batch whose blocks each have their own erasure pattern
+//   rsmi_pair.cpp      rsmi_locate_pair: locate, then the pair of shards that explains an UNKNOWN block
 // No CPU compute path anywhere: every byte of parity, reconstructed data or CRC and every verify
 // flag comes out of the HIP kernels (rs_kernels.hip, rs_kernels_tb.hip, rs_crc16_kernels.hip, rs_crc32_kernels.hip,
-// rs_verify_kernels.hip, rs_locate_kernels.hip, rs_heal_kernels.hip, rs_mixed_kernels.hip).
+// rs_verify_kernels.hip, rs_locate_kernels.hip, rs_heal_kernels.hip, rs_mixed_kernels.hip,
+// rs_pair_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -104,6 +104,12 @@ def lib() -> ctypes.CDLL:
                                                   ctypes.c_void_p, ctypes.c_void_p]),
         "rsmi_locate": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, ctypes.POINTER(ctypes.c_int)]),
         "rsmi_locate_matrix": (ctypes.c_int, [ctypes.c_void_p, u8p]),
+        "rsmi_locate_pair_batch_dev": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, u8p, c_size, c_size, c_size,
+                                                      c_size, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+        "rsmi_locate_pair_batch_host": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, u8p, c_size, c_size, c_size,
+                                                       ctypes.c_void_p, ctypes.c_void_p]),
+        "rsmi_locate_pair": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, ctypes.POINTER(ctypes.c_int)]),
+        "rsmi_locate_pair_checks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, u8p]),
         "rsmi_heal_batch_dev": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, u8p, c_size, c_size, c_size, c_size,
                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
         "rsmi_heal_batch_host": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, u8p, c_size, c_size, c_size,
@@ -245,6 +251,14 @@ class Codec:
         _check(lib().rsmi_locate_matrix(self._h, ctypes.addressof(_buf(out))))
         return bytes(out)
 
+    def locate_pair_checks(self, x: int, y: int) -> bytes:
+        """rsmi_locate_pair_checks: (m - 2) x m check rows C, row-major, with C h_x = C h_y = 0 for the
+        columns of H = [M | I]; the pair {x, y} explains a byte column iff C syn = 0.  Empty for m <= 2."""
+        out = bytearray(max(0, self.m - 2) * self.m)
+        scratch = out if out else bytearray(1)  # the call needs a pointer and writes nothing for m <= 2
+        _check(lib().rsmi_locate_pair_checks(self._h, x, y, ctypes.addressof(_buf(scratch))))
+        return bytes(out)
+
     def set_option(self, key: str, value: int) -> None:
         _check(lib().rsmi_set_option(self._h, key.encode(), int(value)))
 
@@ -304,6 +318,21 @@ class Codec:
         rsmi_verify_batch_host's flags."""
         _check(lib().rsmi_locate_batch_host(self._h, data_ptr, data_bs, parity_ptr, parity_bs, S, nblocks,
                                             culprit_ptr, bad_ptr or None))
+
+    def locate_pair(self, shards, S: int) -> Tuple[int, int]:
+        """rsmi_locate_pair of one block of n*S contiguous bytes: (-1, -1) clean, (x, -1) the single
+        shard rsmi_locate names, (x, y) the one pair of shards that explains the damage, or (-2, -2)."""
+        src = shards if isinstance(shards, bytearray) else bytearray(shards)
+        v = (ctypes.c_int * 2)(LocateUnknown, LocateUnknown)
+        _check(lib().rsmi_locate_pair(self._h, ctypes.addressof(_buf(src)) if src else None, S, v))
+        return v[0], v[1]
+
+    def locate_pair_batch_host_ptr(self, data_ptr: int, data_bs: int, parity_ptr: int, parity_bs: int, S: int,
+                                   nblocks: int, pair_ptr: int, bad_ptr: int = 0) -> None:
+        """rsmi_locate_pair_batch_host: pair_ptr[2b], pair_ptr[2b+1] (int32, host memory) and, when
+        bad_ptr is given, rsmi_verify_batch_host's flags."""
+        _check(lib().rsmi_locate_pair_batch_host(self._h, data_ptr, data_bs, parity_ptr, parity_bs, S, nblocks,
+                                                 pair_ptr, bad_ptr or None))
 
     def heal(self, shards: bytearray, S: int) -> int:
         """rsmi_heal of one block of n*S contiguous bytes, healed in place: the verdict of the
@@ -431,6 +460,14 @@ class Codec:
         rsmi_verify_batch_dev's flags, from one pass over the rows."""
         _check(lib().rsmi_locate_batch_dev(self._h, d_data, data_rs, data_bs, d_parity, parity_rs, parity_bs, S,
                                            nblocks, d_culprit, d_bad or None, stream or None))
+
+    def locate_pair_batch_dev(self, d_data: int, data_rs: int, data_bs: int, d_parity: int, parity_rs: int,
+                              parity_bs: int, S: int, nblocks: int, d_pair: int, d_bad: int = 0,
+                              stream: int = 0) -> None:
+        """rsmi_locate_pair_batch_dev: d_pair[2b], d_pair[2b+1] (int32, device memory) and, when d_bad
+        is given, rsmi_verify_batch_dev's flags.  Stream-ordered."""
+        _check(lib().rsmi_locate_pair_batch_dev(self._h, d_data, data_rs, data_bs, d_parity, parity_rs, parity_bs, S,
+                                                nblocks, d_pair, d_bad or None, stream or None))
 
     def heal_batch_dev(self, d_data: int, data_rs: int, data_bs: int, d_parity: int, parity_rs: int,
                        parity_bs: int, S: int, nblocks: int, d_culprit: int, d_bad: int = 0, stream: int = 0) -> None:
@@ -757,6 +794,17 @@ class Erasure:
         rc, S = check_shards([len(s) if s else 0 for s in shards], nil_ok=False)
         _check(rc)
         return self.encoder().locate(bytearray(b"".join(shards)), S)
+
+    def locate_pair(self, shards: List[bytes]) -> Tuple[int, int]:
+        """Which shards break the stripe (rsmi_locate_pair): (-1, -1) clean, (x, -1) locate's single
+        shard, (x, y) the one pair whose replacement by its reconstruction makes the stripe clean,
+        or (-2, -2).  The shard list is checked as verify checks it."""
+        n = self.data_blocks + self.parity_blocks
+        if len(shards) != n:
+            raise RsmiError(ErrTooFewShards)
+        rc, S = check_shards([len(s) if s else 0 for s in shards], nil_ok=False)
+        _check(rc)
+        return self.encoder().locate_pair(bytearray(b"".join(shards)), S)
 
     def heal(self, shards: List[bytes]) -> Tuple[int, List[bytes]]:
         """Locate, then rewrite the named shard (rsmi_heal): (verdict, shards), the verdict that of

@@ -38,8 +38,10 @@ extern "C" {
  * points (rsmi_verify, rsmi_verify_batch_host, rsmi_verify_batch_dev) joined version 5: additive;
  * so did the locate entry points (rsmi_locate, rsmi_locate_batch_host, rsmi_locate_batch_dev,
  * rsmi_locate_matrix), the heal entry points (rsmi_heal, rsmi_heal_batch_host,
- * rsmi_heal_batch_dev) and the mixed-batch reconstruct (rsmi_reconstruct_mixed_batch_dev,
- * rsmi_reconstruct_mixed_batch_host, rsmi_reconstruct_mixed_classify). */
+ * rsmi_heal_batch_dev), the mixed-batch reconstruct (rsmi_reconstruct_mixed_batch_dev,
+ * rsmi_reconstruct_mixed_batch_host, rsmi_reconstruct_mixed_classify) and the pair locate
+ * (rsmi_locate_pair, rsmi_locate_pair_batch_host, rsmi_locate_pair_batch_dev,
+ * rsmi_locate_pair_checks). */
 #define RSMI_ABI_VERSION 5
 
 typedef struct rsmi_ctx rsmi_ctx;
@@ -263,7 +265,7 @@ int rsmi_verify(rsmi_ctx* ctx, const uint8_t* shards, size_t S, int* ok_out);
  * What the code's distance (m + 1) gives -- a property of the code, not of the implementation:
  *   m = 1        every shard explains any damage, so a dirty stripe is always UNKNOWN;
  *   m >= 2       a single damaged shard, however many of its bytes, is always named;
- *   m >= 2t      t >= 2 damaged shards are always UNKNOWN;
+ *   m >= 2t      t >= 2 damaged shards are always UNKNOWN (rsmi_locate_pair below names two);
  *   beyond that  the damage can imitate a single other shard (its syndromes can be those of
  *                that shard alone); the verdict is then that shard: it is the unique explanation.
  * Every shard is taken as present (there are no missing-shard flags).  The calls are joined to ABI
@@ -295,6 +297,58 @@ int rsmi_locate(rsmi_ctx* ctx, const uint8_t* shards, size_t S, int* culprit_out
  * j >= 1, and parity shard j iff syn_i == 0 for every i != j; the locate kernels' tables are
  * built from R. */
 int rsmi_locate_matrix(const rsmi_ctx* ctx, uint8_t* out);
+
+/* ------------------------------------------------------------------ locate pair: which two shards are wrong */
+
+/* Locate stops at one culprit; with m >= 3 the code can name two.  Let n = k + m and H = [M | I_m],
+ * M the m x k parity part of the encode matrix: column h_x of H is M[.][x] for a data shard x and
+ * the unit vector of row j for parity shard k + j.  syn is Verify's syndrome vector per byte column
+ * over bytes [0, S).
+ *   Explaining pair.  A pair {x, y}, x < y, explains a stripe iff at every byte column syn lies in
+ *   span{h_x, h_y}; equivalently, replacing rows x and y by their reconstruction from the other
+ *   rows yields a clean stripe.  Padding never counts.
+ *   Verdict.  Two int32 per block, out[2b] and out[2b+1]:
+ *     (-1, -1)       the stripe is clean;
+ *     (x, -1)        rsmi_locate names the single shard x (unchanged from rsmi_locate; no pair test
+ *                    is run for such a block);
+ *     (x, y), x < y  no single shard explains the stripe and exactly one pair does;
+ *     (-2, -2)       every other case.
+ *   For m >= 2 rsmi_locate's UNKNOWN means that no single shard explains the stripe, so every
+ *   explaining pair found behind it is a genuine pair.
+ * What the code's distance (m + 1) gives -- a property of the code, not of the implementation:
+ *   m <= 2        no pair is ever named: every pair explains everything.  Such contexts get
+ *                 rsmi_locate's verdicts widened to two words;
+ *   m = 3         a pair is named when it happens to be the only one; that is not guaranteed;
+ *   m >= 4        two damaged shards are always named;
+ *   three or more damaged shards: the verdict is (-2, -2), or the damage imitates a pair, which
+ *                 is then that block's unique explanation.
+ * A named pair is repaired by rsmi_reconstruct_mixed_batch_* with the two shards absent and
+ * required.  Layout, argument checks, their order and their statuses are those of rsmi_locate_*.
+ * The calls are joined to ABI version 5 (additive); none of them takes or clears the per-thread
+ * wait hook. */
+
+/* Device-resident.  d_pair_out (device memory, 2 * nblocks verdict words) and, when d_bad_out is not
+ * NULL, d_bad_out[b*m + j], exactly rsmi_verify_batch_dev's flags.  Nothing else is written.
+ * Stream-ordered, no sync (scratch is kept per stream; growing it waits for that stream once). */
+int rsmi_locate_pair_batch_dev(rsmi_ctx* ctx, const uint8_t* d_data, size_t data_shard_stride,
+                               size_t data_block_stride, const uint8_t* d_parity, size_t parity_shard_stride,
+                               size_t parity_block_stride, size_t S, size_t nblocks, int32_t* d_pair_out,
+                               uint32_t* d_bad_out, void* stream);
+
+/* Host memory, layout and the three paths of rsmi_verify_batch_host; pair_out[2b], pair_out[2b+1]
+ * and (when not NULL) bad_out[b*m + j] in host memory. */
+int rsmi_locate_pair_batch_host(rsmi_ctx* ctx, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
+                                size_t parity_block_stride, size_t S, size_t nblocks, int32_t* pair_out,
+                                uint32_t* bad_out);
+
+/* One block of n*S contiguous bytes: pair_out[0], pair_out[1] receive its verdict. */
+int rsmi_locate_pair(rsmi_ctx* ctx, const uint8_t* shards, size_t S, int pair_out[2]);
+
+/* Host-only, works without a GPU: m - 2 linearly independent rows c_i (m bytes each, row-major in
+ * out) with c_i . h_x = c_i . h_y = 0, so {x, y} explains a byte column iff every c_i . syn = 0.
+ * The pair kernels' tables are built from these rows.  m <= 2: nothing is written, RSMI_OK.
+ * x == y or an index outside [0, n): RSMI_ERR_INVALID_ARG. */
+int rsmi_locate_pair_checks(const rsmi_ctx* ctx, int x, int y, uint8_t* out);
 
 /* ------------------------------------------------------------------ heal: rewrite the shard that is wrong */
 
