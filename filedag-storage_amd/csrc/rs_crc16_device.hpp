@@ -6,13 +6,11 @@
 
 #include <cstdint>
 
+#include "rs_crc_rows.hpp"
 #include "rs_device.hpp"
 #include "rs_plan.hpp"
 
 namespace rsmi {
-
-typedef int mfma_v8i __attribute__((ext_vector_type(8)));
-typedef float mfma_v4f __attribute__((ext_vector_type(4)));
 
 // A^(2^i)(s) through the nibble-sliced tables P4[i][4][16]
 __device__ __forceinline__ uint32_t crc_pow4(const uint16_t* sQ, int i, uint32_t s) {
@@ -25,13 +23,7 @@ __device__ __forceinline__ uint32_t crc_pow4(const uint16_t* sQ, int i, uint32_t
 // relative to the end of chunk 48 + m; a 4-level scan over the 16 lanes (A^(16 * 2^j)) leaves
 // sum_m A^(16 (15 - m)) (class m), the value relative to the end of chunk 63, in lane 15 of the row.
 __device__ __forceinline__ uint32_t crc_class_scan(const uint16_t* sQ, uint32_t acc, uint32_t m) {
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const uint32_t w = crc_pow4(sQ, 4 + j, acc);  // 16 * 2^j bytes
-        const uint32_t t = __shfl_up(w, 1u << j);
-        if (m >= (1u << j)) acc ^= t;
-    }
-    return acc;
+    return rows_scan<4>(acc, m, [&](int j, uint32_t a) { return crc_pow4(sQ, 4 + j, a); });  // 16 * 2^j bytes
 }
 
 // R(row) of rows 4 p + g (lane l = 16 g + m: class m) of one block from its unit records

@@ -22,6 +22,7 @@
 
 #include "crc16.hpp"
 #include "rs_crc16_device.hpp"
+#include "rs_crc_rows.hpp"
 #include "rs_device.hpp"
 #include "rs_plan.hpp"
 
@@ -73,70 +74,47 @@ __device__ __forceinline__ void crc_item_add(const uint16_t* sQ, uint32_t lane, 
 // The item's value -> row word: lane scan, then crc_item_add.
 __device__ __forceinline__ void crc_item_out(const uint16_t* sQ, uint32_t lane, uint32_t acc, uint64_t item_end,
                                              uint64_t last_end, uint32_t col_e, uint32_t* word) {
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-        const uint32_t w = crc_pow4(sQ, 4 + j, acc);  // 16 * 2^j bytes
-        const uint32_t t = __shfl_up(w, 1u << j);
-        if (lane >= (1u << j)) acc ^= t;
-    }
+    acc = rows_scan<6>(acc, lane, [&](int j, uint32_t a) { return crc_pow4(sQ, 4 + j, a); });  // 16 * 2^j bytes
     const uint32_t val = uint32_t(__builtin_amdgcn_readlane(int(acc), kWave - 1));  // wave-uniform from here
     crc_item_add(sQ, lane, val, uint32_t((last_end - item_end) % kCrcOrder), col_e, word);
 }
 
-// Position of item `it` (nsup items per row): its row and first tile.
-struct CrcItem {
-    uint64_t b;
-    uint32_t r, t0, nt;  // block, row in block, first tile, tiles in the item
-};
-__device__ __forceinline__ CrcItem crc_item(uint64_t it, uint32_t nsup, uint32_t nrows, uint32_t tpb) {
-    constexpr uint32_t kSup = kCrcSupGroups * kCrcSegTiles;
-    CrcItem x;
-    uint32_t sup;
-    if (it < (uint64_t(1) << 32)) {  // 32-bit divisions (scalar), the common case
-        const uint32_t i32 = uint32_t(it), rid = i32 / nsup;
-        sup = i32 - rid * nsup;
-        const uint32_t b = rid / nrows;
-        x.b = b;
-        x.r = rid - b * nrows;
-    } else {
-        sup = uint32_t(it % nsup);
-        const uint64_t rid = it / nsup;
-        x.b = rid / nrows;
-        x.r = uint32_t(rid - x.b * nrows);
-    }
-    x.t0 = sup * kSup;
-    x.nt = tpb - x.t0 < kSup ? tpb - x.t0 : kSup;
-    return x;
-}
-// the byte the item's value is relative to: the end of its last group, counted as 8 tiles
-__device__ __forceinline__ uint64_t crc_item_end(const CrcItem& x) {
+// the byte an item's value is relative to: the end of its last group, counted as 8 tiles; and the
+// row's last item's (the launch's A^E starts there)
+__device__ __forceinline__ uint64_t crc_item_end(const RowsItem& x) {
     return (uint64_t(x.t0) + (x.nt + kCrcSegTiles - 1) / kCrcSegTiles * kCrcSegTiles) * (kWave * 16);
 }
+__device__ __forceinline__ uint64_t crc_last_end(uint32_t tpb) {
+    return (uint64_t(tpb) + kCrcSegTiles - 1) / kCrcSegTiles * kCrcSegTiles * (kWave * 16);
+}
 
-// LDS staging shared by the rows passes: P4, then G
-#define RSMI_CRC_ROWS_STAGE()                                                                             \
-    __shared__ uint32_t s_tbl[kCrcP4Words + kCrcGWords];                                                  \
-    for (int i = threadIdx.x; i < kCrcP4Words; i += kWG) s_tbl[i] = tbl[kCrcP4Off + i];                   \
-    for (int i = threadIdx.x; i < kCrcGWords; i += kWG) s_tbl[kCrcP4Words + i] = tbl[kCrcGOff + i];       \
-    __syncthreads();                                                                                      \
-    const uint16_t* sQ = reinterpret_cast<const uint16_t*>(s_tbl);                                        \
-    const uint8_t* nb = reinterpret_cast<const uint8_t*>(s_tbl + kCrcP4Words); /* G[8][32][16] */  \
-    uint32_t col_e = 0; /* A^E, lane-distributed */                                                    \
-    _Pragma("unroll") for (int b_ = 0; b_ < 16; b_++) col_e = (threadIdx.x & 15u) == uint32_t(b_) ? sh.col[b_] : col_e; \
-    const uint64_t last_end = (uint64_t(tpb) + kCrcSegTiles - 1) / kCrcSegTiles * kCrcSegTiles * (kWave * 16);
+// LDS staging of the nibble passes: P4, then G[8][32][16]
+struct CrcNibTables {
+    const uint16_t* sQ;
+    const uint8_t* nb;
+};
+__device__ __forceinline__ CrcNibTables crc_stage_nib(uint32_t (&s_tbl)[kCrcP4Words + kCrcGWords], const uint32_t* tbl) {
+    for (int i = threadIdx.x; i < kCrcP4Words; i += kWG) s_tbl[i] = tbl[kCrcP4Off + i];
+    for (int i = threadIdx.x; i < kCrcGWords; i += kWG) s_tbl[kCrcP4Words + i] = tbl[kCrcGOff + i];
+    __syncthreads();
+    return CrcNibTables{reinterpret_cast<const uint16_t*>(s_tbl), reinterpret_cast<const uint8_t*>(s_tbl + kCrcP4Words)};
+}
 
-template <bool ALIGNED>
+// The nibble pass for rows at any byte alignment: byte-aligned loads on the row's own grid
+// (crc_chunk_load), a group's loads issued before its folds.
 __global__ __launch_bounds__(kWG) void rs_crc16_rows_kernel(const uint32_t* __restrict__ tbl,
                                                             const uint8_t* __restrict__ base, uint64_t bstride,
                                                             uint64_t rpitch, uint32_t nrows, uint64_t S, uint32_t tpb,
                                                             uint32_t nsup, uint64_t nitems, uint32_t* __restrict__ out,
                                                             uint64_t out_bs, Crc16Shift sh) {
-    RSMI_CRC_ROWS_STAGE()
-    const uint32_t lane = threadIdx.x & (kWave - 1);
-    const uint32_t wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-    const uint64_t nw = uint64_t(gridDim.x) * (kWG / kWave);
-    for (uint64_t it = uint64_t(blockIdx.x) * (kWG / kWave) + wid; it < nitems; it += nw) {
-        const CrcItem x = crc_item(it, nsup, nrows, tpb);
+    __shared__ uint32_t s_tbl[kCrcP4Words + kCrcGWords];
+    const CrcNibTables T = crc_stage_nib(s_tbl, tbl);
+    const uint32_t col_e = lane_column(sh.col);  // A^E, lane-distributed
+    const uint64_t last_end = crc_last_end(tpb);
+    const RowsWave wv = rows_wave<kWG>();
+    const uint32_t lane = wv.lane;
+    for (uint64_t it = wv.it0; it < nitems; it += wv.nw) {
+        const RowsItem x = rows_item(it, nsup, nrows, tpb);
         const uint8_t* row = base + x.b * bstride + uint64_t(x.r) * rpitch;
         uint32_t acc = 0;
         for (uint32_t g0 = 0; g0 < x.nt; g0 += kCrcSegTiles) {
@@ -145,135 +123,57 @@ __global__ __launch_bounds__(kWG) void rs_crc16_rows_kernel(const uint32_t* __re
             u32x4 v[kCrcSegTiles];
 #pragma unroll
             for (int i = 0; i < kCrcSegTiles; i++)
-                if (uint32_t(i) < nt) {
-                    const uint64_t off = (uint64_t(t0 + i) * kWave + lane) * 16;
-                    // wave-uniform: only a row's last tile needs the per-lane bounds and masks
-                    if (ALIGNED && (uint64_t(t0 + i) + 1) * (kWave * 16) <= S)
-                        v[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(row + off));
-                    else
-                        v[i] = crc_chunk_load<ALIGNED>(row, off, S);
-                }
+                if (uint32_t(i) < nt) v[i] = crc_chunk_load(row, (uint64_t(t0 + i) * kWave + lane) * 16, S);
             uint32_t gs = 0;  // the group's value, relative to the end of its 8th tile
 #pragma unroll
             for (int i = 0; i < kCrcSegTiles; i++)
-                if (uint32_t(i) < nt) gs ^= crc_nib_chunk(nb + 1024 * i, v[i]);
-            acc = crc_pow4(sQ, 13, acc) ^ gs;  // earlier groups move 8 KiB further from the end
+                if (uint32_t(i) < nt) gs ^= crc_nib_chunk(T.nb + 1024 * i, v[i]);
+            acc = crc_pow4(T.sQ, 13, acc) ^ gs;  // earlier groups move 8 KiB further from the end
         }
-        crc_item_out(sQ, lane, acc, crc_item_end(x), last_end, col_e, out + x.b * out_bs + x.r);
+        crc_item_out(T.sQ, lane, acc, crc_item_end(x), last_end, col_e, out + x.b * out_bs + x.r);
     }
 }
 
-// The nibble rows pass, software-pipelined, for 16-byte-aligned rows (the default).  A wave
-// works in units of half a group (4 tiles) and issues the loads of its next unit (of this item
-// or its next one) before it folds the current one (two register sets of 16 VGPRs, the loop
-// unrolled by two), so its own fold covers the next unit's memory latency instead of only the
-// other waves on the SIMD; half-group units keep the kernel under 64 VGPRs (8 waves per SIMD,
-// with 12 KiB of LDS per workgroup).  Loads are unconditional -- chunks past the row's end read
-// the row's last chunk and are masked to zero in the fold, and the prefetch past the wave's
-// last unit re-reads that unit -- so no load sits behind a branch and the compiler's vmcnt
-// waits count only the older set.
+// The nibble pass for 16-byte-aligned rows (the default): rows_pipe (rs_crc_rows.hpp) with the
+// tile-set tables G, A^8192 from P4 and crc_item_out; 12 KiB of LDS per workgroup.
 __global__ __launch_bounds__(kWG) void rs_crc16_rows_pipe_kernel(const uint32_t* __restrict__ tbl,
                                                                  const uint8_t* __restrict__ base, uint64_t bstride,
                                                                  uint64_t rpitch, uint32_t nrows, uint64_t S,
                                                                  uint32_t tpb, uint32_t nsup, uint64_t nitems,
                                                                  uint32_t* __restrict__ out, uint64_t out_bs,
                                                                  Crc16Shift sh) {
-    RSMI_CRC_ROWS_STAGE()
-    constexpr int kU = kCrcSegTiles / 2;  // tiles per unit
-    const uint32_t lane = threadIdx.x & (kWave - 1);
-    const uint32_t wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-    const uint64_t nw = uint64_t(gridDim.x) * (kWG / kWave);
-    const uint64_t last = (S - 1) / 16 * 16;  // the row's last chunk (S > 0)
-    // a unit of work: tiles t0 + 4 h .. t0 + 4 h + 3 of item it (its position computed once per item)
-    struct Unit {
-        uint64_t it;
-        CrcItem x;
-        uint32_t h;
-    };
-    auto at = [&](uint64_t it) -> Unit { return Unit{it, crc_item(it, nsup, nrows, tpb), 0}; };
-    auto next = [&](const Unit& u) -> Unit {
-        if ((u.h + 1) * kU < u.x.nt) return Unit{u.it, u.x, u.h + 1};
-        return at(u.it + nw);
-    };
-    auto issue = [&](const Unit& u, u32x4(&v)[kU]) {
-        const uint8_t* row = base + u.x.b * bstride + uint64_t(u.x.r) * rpitch;
-#pragma unroll
-        for (int i = 0; i < kU; i++) {
-            const uint64_t off = (uint64_t(u.x.t0 + u.h * kU + i) * kWave + lane) * 16;
-            v[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(row + (off < last ? off : last)));
-        }
-    };
-    uint32_t acc = 0, gs = 0;
-    auto finish = [&](const Unit& u, u32x4(&v)[kU]) {
-        const CrcItem& x = u.x;
-        const uint32_t u0 = u.h * kU, t0 = x.t0 + u0;
-        const uint32_t nt = x.nt - u0 < uint32_t(kU) ? x.nt - u0 : uint32_t(kU);
-        const uint8_t* gt = nb + 1024 * kU * (u.h & 1);  // table sets of this half of the group
-#pragma unroll
-        for (int i = 0; i < kU; i++) {
-            if (uint32_t(i) < nt) {
-                if ((uint64_t(t0 + i) + 1) * (kWave * 16) > S) {  // wave-uniform: the row's last tile
-                    const int64_t valid = int64_t(S) - int64_t((uint64_t(t0 + i) * kWave + lane) * 16);
-#pragma unroll
-                    for (int w = 0; w < 4; w++) v[i][w] &= bytes_mask(valid - 4 * w);
-                }
-                gs ^= crc_nib_chunk(gt + 1024 * i, v[i]);
-            }
-        }
-        const bool item_end = u0 + kU >= x.nt;
-        if ((u.h & 1) || item_end) {  // the group is complete
-            acc = crc_pow4(sQ, 13, acc) ^ gs;  // earlier groups move 8 KiB further from the end
-            gs = 0;
-        }
-        if (item_end) {
-            crc_item_out(sQ, lane, acc, crc_item_end(x), last_end, col_e, out + x.b * out_bs + x.r);
-            acc = 0;
-        }
-    };
-    const uint64_t it0 = uint64_t(blockIdx.x) * (kWG / kWave) + wid;
-    if (it0 >= nitems) return;
-    Unit cur = at(it0);
-    u32x4 va[kU], vb[kU];
-    issue(cur, va);
-    for (;;) {
-        Unit nx = next(cur);
-        bool more = nx.it < nitems;
-        issue(more ? nx : cur, vb);
-        finish(cur, va);
-        if (!more) break;
-        cur = nx;
-        nx = next(cur);
-        more = nx.it < nitems;
-        issue(more ? nx : cur, va);
-        finish(cur, vb);
-        if (!more) break;
-        cur = nx;
-    }
+    __shared__ uint32_t s_tbl[kCrcP4Words + kCrcGWords];
+    const CrcNibTables T = crc_stage_nib(s_tbl, tbl);
+    const uint32_t col_e = lane_column(sh.col);  // A^E, lane-distributed
+    const uint64_t last_end = crc_last_end(tpb);
+    const RowsWave wv = rows_wave<kWG>();
+    const uint32_t lane = wv.lane;
+    rows_pipe<false>(
+        wv, base, bstride, rpitch, nrows, S, tpb, nsup, nitems,
+        [&](uint32_t i, const u32x4& v) { return crc_nib_chunk(T.nb + 1024 * i, v); },
+        [&](uint32_t acc) { return crc_pow4(T.sQ, 13, acc); },
+        [&](uint32_t acc, const RowsItem& x, uint32_t) {
+            crc_item_out(T.sQ, lane, acc, crc_item_end(x), last_end, col_e, out + x.b * out_bs + x.r);
+        });
 }
 
-// The rows pass with the fold on the matrix cores, aligned rows.  R(chunk) is
+// The rows pass with the fold on the matrix cores.  R(chunk) is
 // GF(2)-linear in the chunk's 128 bits, so a tile's fold is a GF(2) matrix product; the fp4
 // MFMA v_mfma_scale_f32_16x16x128_f8f6f4 sums integer products exactly, and bit 0 of each count
-// is the product's bit.  B = the tile's data, one data bit per fp4 nibble (v & 0x11111111,
-// 0x22.., 0x44.., (v >> 1) & 0x44..; bit 3 is the e2m1 sign), column m = lane & 15, k block
-// j = lane >> 4 (chunk 16 j + m); A = the weights of tile t of an 8-tile group (MW, in LDS,
-// one ds_read_b128 per MFMA), row n = CRC bit; every product of a set data bit and a set weight
-// is 1.0.  The counts of a whole group accumulate in one f32 quad (at most 4096 per count), so
-// the parity is read once per group: four ballots, and lane m (< 16) gathers class m's value
-// (chunks m, m + 16, m + 32, m + 48 of the group's tiles, relative to the end of chunk 48 + m
-// of tile 7).  Groups step by A^8192 as in the nibble pass; at the item's end a 4-level scan
-// over lanes 0..15 (A^(16 * 2^j)) leaves the value relative to the group's end in lane 15, and
-// the shift to the row's end is the nibble pass's.  4 MFMAs and 20 VALU per tile fold what the
-// nibble tables fold with 32 lookups and ~70 VALU.
+// is the product's bit.  B = the tile's data, one data bit per fp4 nibble (fp4_bit_plane),
+// column m = lane & 15, k block j = lane >> 4 (chunk 16 j + m); A = the weights of tile t of an
+// 8-tile group (MW, in LDS, one ds_read_b128 per MFMA), row n = CRC bit; every product of a set
+// data bit and a set weight is 1.0.  The counts of a whole group accumulate in one f32 quad (at
+// most 4096 per count), so the parity is read once per group (ballot_class_value): lane m (< 16)
+// gathers class m's value (chunks m, m + 16, m + 32, m + 48 of the group's tiles, relative to the
+// end of chunk 48 + m of tile 7).  Groups step by A^8192 as in the nibble pass; at the item's end a
+// 4-level scan over lanes 0..15 (A^(16 * 2^j)) leaves the value relative to the group's end in
+// lane 15, and the shift to the row's end is the nibble pass's.  4 MFMAs and 20 VALU per tile fold
+// what the nibble tables fold with 32 lookups and ~70 VALU.
 //
-// UA: rows at any byte alignment (the Split layout: rows back to back at pitch S).  The fold runs
-// on the memory's 16-byte grid instead of the row's: the row's bytes are folded where they lie,
-// from the aligned chunk at or below the row's first byte (its mis = row & 15 leading bytes, the
-// previous row's tail, masked to zero) to the aligned chunk holding its last byte (bytes past it
-// masked), so every load is the aligned pass's and no data moves between lanes.  Only the reference
-// point changes: an item's value is relative to its end on that grid, mis bytes before its end on
-// the row's grid, so the shift to the row's end takes mis bytes more (the launch's tiles per row
-// count mis + S bytes, S + 15 at most).
+// UA: rows at any byte alignment (the Split layout: rows back to back at pitch S) fold on the
+// memory's 16-byte grid (RowSpan, rs_crc_rows.hpp), so every load is the aligned pass's; the shift
+// to the row's end takes mis bytes more.
 template <bool UA>
 __global__ __launch_bounds__(kWG) void rs_crc16_rows_mfma_kernel(const uint32_t* __restrict__ tbl,
                                                                  const uint8_t* __restrict__ base, uint64_t bstride,
@@ -288,75 +188,42 @@ __global__ __launch_bounds__(kWG) void rs_crc16_rows_mfma_kernel(const uint32_t*
         s_w[i] = reinterpret_cast<const u32x4*>(tbl + kCrcMWOff)[i];
     __syncthreads();
     const uint16_t* sQ = reinterpret_cast<const uint16_t*>(s_p4);
-    uint32_t col_e = 0;  // A^E, lane-distributed
-#pragma unroll
-    for (int b = 0; b < 16; b++) col_e = (threadIdx.x & 15u) == uint32_t(b) ? sh.col[b] : col_e;
-    const uint64_t last_end = (uint64_t(tpb) + kCrcSegTiles - 1) / kCrcSegTiles * kCrcSegTiles * (kWave * 16);
-    const uint32_t lane = threadIdx.x & (kWave - 1), m = lane & 15u;
-    const uint32_t wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-    const uint64_t nw = uint64_t(gridDim.x) * (kWG / kWave);
-    for (uint64_t it = uint64_t(blockIdx.x) * (kWG / kWave) + wid; it < nitems; it += nw) {
-        const CrcItem x = crc_item(it, nsup, nrows, tpb);
-        const uint8_t* row = base + x.b * bstride + uint64_t(x.r) * rpitch;
-        // UA: the row's misalignment (wave-uniform), its aligned base and the aligned chunk that
-        // holds its last byte
-        const uint32_t mis = UA ? uint32_t(__builtin_amdgcn_readfirstlane(int(reinterpret_cast<uintptr_t>(row) & 15u))) : 0u;
-        const uint8_t* rowa = row - mis;
-        const uint64_t Sm = mis + S;  // the row's end on the memory grid
-        const uint64_t lasta = (Sm - 1) / 16 * 16;
+    const uint32_t col_e = lane_column(sh.col);  // A^E, lane-distributed
+    const uint64_t last_end = crc_last_end(tpb);
+    const RowsWave wv = rows_wave<kWG>();
+    const uint32_t lane = wv.lane, m = lane & 15u;
+    for (uint64_t it = wv.it0; it < nitems; it += wv.nw) {
+        const RowsItem x = rows_item(it, nsup, nrows, tpb);
+        const RowSpan<UA> sp = row_span<UA>(base + x.b * bstride + uint64_t(x.r) * rpitch, S);
         uint32_t acc = 0;  // lanes 0..15: class m's running value
         for (uint32_t g0 = 0; g0 < x.nt; g0 += kCrcSegTiles) {
             const uint32_t t0 = x.t0 + g0;
             const uint32_t nt = x.nt - g0 < uint32_t(kCrcSegTiles) ? x.nt - g0 : uint32_t(kCrcSegTiles);
             u32x4 v[kCrcSegTiles];
 #pragma unroll
-            for (int i = 0; i < kCrcSegTiles; i++) {
-                const uint64_t off = (uint64_t(t0 + i) * kWave + lane) * 16;  // unconditional, clamped
-                v[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(rowa + (off < lasta ? off : lasta)));
-            }
+            for (int i = 0; i < kCrcSegTiles; i++) v[i] = sp.load(t0 + i, lane);
             mfma_v4f c = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int i = 0; i < kCrcSegTiles; i++) {
                 if (uint32_t(i) < nt) {
                     u32x4 d = v[i];
-                    if ((uint64_t(t0 + i) + 1) * (kWave * 16) > Sm) {  // wave-uniform: the row's last tile
-                        const int64_t valid = int64_t(Sm) - int64_t((uint64_t(t0 + i) * kWave + lane) * 16);
-#pragma unroll
-                        for (int w = 0; w < 4; w++) d[w] &= bytes_mask(valid - 4 * w);
-                    }
-                    if (UA && t0 + i == 0 && mis != 0u && lane == 0) {  // UA: the bytes before the row
-#pragma unroll
-                        for (int w = 0; w < 4; w++) d[w] &= ~bytes_mask(int(mis) - 4 * w);  // dword w's leading bytes dropped
-                    }
+                    mask_row_ends<UA>(d, t0 + i, lane, sp);
 #pragma unroll
                     for (int q = 0; q < 4; q++) {
-                        mfma_v8i bd;
-#pragma unroll
-                        for (int w = 0; w < 4; w++)
-                            bd[w] = int(q < 3 ? d[w] & (0x11111111u << q) : (d[w] >> 1) & 0x44444444u);
-                        bd[4] = bd[5] = bd[6] = bd[7] = 0;
+                        const mfma_v8i bd = fp4_bit_plane(d, q);
                         const u32x4 wt = s_w[(i * 4 + q) * kWave + lane];
                         const mfma_v8i aw = {int(wt[0]), int(wt[1]), int(wt[2]), int(wt[3]), 0, 0, 0, 0};
                         c = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(aw, bd, c, 4, 4, 0, 127, 0, 127);
                     }
                 }
             }
-            // parity bits -> class m's 16-bit value: bit n of class m is bit 16 (n >> 2) + m of
-            // ballot n & 3
-            uint32_t Y = 0;
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const uint64_t bl = __builtin_amdgcn_ballot_w64((int(c[i]) & 1) != 0);
-                const uint32_t lo = uint32_t(bl) >> m, hi = uint32_t(bl >> 32) >> m;
-                Y |= ((lo & 0x10001u) | ((hi & 0x10001u) << 8)) << i;  // n = i, 4 + i (bit 16), 8 + i, 12 + i (bit 24)
-            }
-            const uint32_t val = (Y & 0x0F0Fu) | ((Y >> 12) & 0xF0F0u);
-            acc = crc_pow4(sQ, 13, acc) ^ val;  // earlier groups move 8 KiB further from the end
+            // earlier groups move 8 KiB further from the end
+            acc = crc_pow4(sQ, 13, acc) ^ ballot_class_value(c, m);
         }
         // classes -> the group's end, in lane 15 (wave-uniform from here)
         const uint32_t val = uint32_t(__builtin_amdgcn_readlane(int(crc_class_scan(sQ, acc, m)), 15));
         // UA: the item's end lies mis bytes before its end on the row's grid
-        crc_item_add(sQ, lane, val, uint32_t((last_end - crc_item_end(x) + mis) % kCrcOrder), col_e,
+        crc_item_add(sQ, lane, val, uint32_t((last_end - crc_item_end(x) + sp.mis) % kCrcOrder), col_e,
                      out + x.b * out_bs + x.r);
     }
 }
@@ -481,7 +348,7 @@ void* crc16_combine_kernel(int ns2) {
 // aligned rows: the pipelined pass; any other layout: the plain nibble pass
 void* crc16_rows_kernel(bool aligned) {
     return aligned ? reinterpret_cast<void*>(&rs_crc16_rows_pipe_kernel)
-                   : reinterpret_cast<void*>(&rs_crc16_rows_kernel<false>);
+                   : reinterpret_cast<void*>(&rs_crc16_rows_kernel);
 }
 
 }  // namespace rsmi

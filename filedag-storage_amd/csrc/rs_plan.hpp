@@ -299,7 +299,7 @@ struct Crc16Shift {
     uint32_t col[16];
 };
 void* crc16_rows_kernel(bool aligned);
-void* crc16_rows_mfma_kernel(bool aligned);  // the fold on the matrix cores (unaligned rows: funnel-shifted aligned loads)
+void* crc16_rows_mfma_kernel(bool aligned);  // the fold on the matrix cores (unaligned rows: folded on the memory's 16-byte grid)
 void* crc16_combine_kernel(int ns2);  // ns2 = record dwords per lane (rows / 8, rounded up)
 void* crc16_combine_mfma_kernel();    // records of rs_fused_mfma_kernel
 void* crc32_rows_kernel(bool aligned);

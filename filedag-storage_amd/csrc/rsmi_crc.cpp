@@ -31,6 +31,38 @@ int ensure_crc_tables(rsmi_ctx* c) {
     return RSMI_OK;
 }
 
+namespace {
+
+// every row of the launch starts on the memory's 16-byte grid
+bool rows_aligned(const uint8_t* base, uint64_t rpitch, uint64_t bstride) {
+    return reinterpret_cast<uintptr_t>(base) % 16 == 0 && rpitch % 16 == 0 && bstride % 16 == 0;
+}
+
+// A rows launch's work (rs_crc_rows.hpp): the tiles a row of `span` bytes takes, its items (up to
+// 32 tiles each), the launch's items, and the persistent grid of wpg-wave workgroups.
+// The grid is capped at wpc waves per CU (option waves_per_cu overrides): several dispatch
+// rounds, so the hardware balances CUs (items differ in length at a row's end), while each
+// workgroup still amortizes its LDS table staging over a few items per wave.
+struct RowsGrid {
+    uint32_t tpb, nsup;
+    uint64_t nitems;
+    uint32_t wgs;
+};
+RowsGrid rows_grid(const rsmi_ctx* c, uint64_t span, uint32_t nrows, uint64_t nblocks, uint64_t wpg, uint64_t wpc) {
+    constexpr uint64_t kTile = uint64_t(kWave) * 16, kSup = kCrcSupGroups * kCrcSegTiles;
+    static_assert(kCrc32SupGroups * kCrc32SegTiles == kSup, "one item shape");
+    RowsGrid g;
+    g.tpb = uint32_t((span + kTile - 1) / kTile);
+    g.nsup = uint32_t((g.tpb + kSup - 1) / kSup);
+    g.nitems = nblocks * nrows * g.nsup;
+    uint64_t cap = uint64_t(c->num_cu) * wpc / wpg;
+    if (c->opt_waves_per_cu > 0) cap = std::max<uint64_t>(1, uint64_t(c->num_cu) * uint64_t(c->opt_waves_per_cu) / wpg);
+    g.wgs = uint32_t(std::min<uint64_t>((g.nitems + wpg - 1) / wpg, cap));
+    return g;
+}
+
+}  // namespace
+
 // R(row) of nrows rows per block into out[b*out_bs + r] (zeroed first), stream-ordered.
 int launch_crc(rsmi_ctx* c, const uint8_t* base, uint64_t rpitch, uint64_t bstride, uint32_t nrows, uint64_t S,
                uint64_t nblocks, uint32_t* out, uint64_t out_bs, hipStream_t stream, bool zero) {
@@ -39,33 +71,22 @@ int launch_crc(rsmi_ctx* c, const uint8_t* base, uint64_t rpitch, uint64_t bstri
     if (rc) return rc;
     if (zero) HIP_TRY(hipMemset2DAsync(out, out_bs * 4, 0, size_t(nrows) * 4, nblocks, stream));
     if (S == 0) return RSMI_OK;  // R(empty) = 0
-    const bool aligned = reinterpret_cast<uintptr_t>(base) % 16 == 0 && rpitch % 16 == 0 && bstride % 16 == 0;
-    // the fold on the matrix cores for any layout (unaligned rows: aligned loads funnel-shifted),
-    // option crc16_fold 0: the nibble-table passes
-    void* fn = c->opt_crc16_fold == 1 ? crc16_rows_mfma_kernel(aligned) : crc16_rows_kernel(aligned);
-    const uint64_t tile = uint64_t(kWave) * 16;
+    const bool aligned = rows_aligned(base, rpitch, bstride);
+    // the fold on the matrix cores for any layout, option crc16_fold 0: the nibble-table passes
+    const bool mfma = c->opt_crc16_fold == 1;
+    void* fn = mfma ? crc16_rows_mfma_kernel(aligned) : crc16_rows_kernel(aligned);
     // the matrix-core pass folds unaligned rows on the memory's 16-byte grid, where a row spans
-    // its misalignment (< 16) + S bytes
-    const uint64_t span = S + (c->opt_crc16_fold == 1 && !aligned ? 15 : 0);
-    uint32_t tpb = uint32_t((span + tile - 1) / tile);
-    constexpr uint32_t kSup = kCrcSupGroups * kCrcSegTiles;
-    uint32_t nsup = (tpb + kSup - 1) / kSup;
-    uint64_t nitems = nblocks * nrows * nsup;
+    // its misalignment (< 16) + S bytes.  96 waves per CU: level with 48 and 64 at 26 KB rows,
+    // +10 % at 256 KB rows (profiles/r02/crc/crc_rows_grid.txt).
+    RowsGrid g = rows_grid(c, S + (mfma && !aligned ? 15 : 0), nrows, nblocks, kWG / kWave, 96);
     // A^E, E = S - (end of the last item, counted in whole 8-tile groups), mod 32767
-    const uint64_t last_end = (uint64_t(tpb) + kCrcSegTiles - 1) / kCrcSegTiles * kCrcSegTiles * tile;
+    const uint64_t last_end = (uint64_t(g.tpb) + kCrcSegTiles - 1) / kCrcSegTiles * kCrcSegTiles * kWave * 16;
     const int64_t E = ((int64_t(S) - int64_t(last_end)) % int64_t(kCrcOrder) + kCrcOrder) % kCrcOrder;
     Crc16Shift sh;
     for (int b = 0; b < 16; b++) sh.col[b] = crc16_tables().shift(uint16_t(1u << b), uint64_t(E));
-    // 96 waves per CU: several dispatch rounds, so the hardware balances CUs (items differ in
-    // length at a row's end), while each workgroup still amortizes its LDS table staging over
-    // a few items per wave.  Level with 48 and 64 at 26 KB rows, +10 % at 256 KB rows
-    // (profiles/r02/crc/crc_rows_grid.txt).
-    uint64_t cap = uint64_t(c->num_cu) * 96 / 4;
-    if (c->opt_waves_per_cu > 0) cap = std::max<uint64_t>(1, uint64_t(c->num_cu) * uint64_t(c->opt_waves_per_cu) / 4);
-    const uint64_t wgs = std::min<uint64_t>((nitems + 3) / 4, cap);
     const uint32_t* tb = c->d_crc_tbl;
-    void* args[] = {&tb, &base, &bstride, &rpitch, &nrows, &S, &tpb, &nsup, &nitems, &out, &out_bs, &sh};
-    HIP_TRY(hipLaunchKernel(fn, dim3(uint32_t(wgs)), dim3(kWG), args, 0, stream));
+    void* args[] = {&tb, &base, &bstride, &rpitch, &nrows, &S, &g.tpb, &g.nsup, &g.nitems, &out, &out_bs, &sh};
+    HIP_TRY(hipLaunchKernel(fn, dim3(g.wgs), dim3(kWG), args, 0, stream));
     return RSMI_OK;
 }
 
@@ -91,39 +112,31 @@ int ensure_crc32_tables(rsmi_ctx* c) {
 
 // CRC-32 R(row) of nrows rows per block, XORed into out[b*out_bs + r] (the caller zeroes
 // it), stream-ordered.  Rows may lie in device or page-locked host memory.
-
 int launch_crc32(rsmi_ctx* c, const uint8_t* base, uint64_t rpitch, uint64_t bstride, uint32_t nrows, uint64_t S,
                  uint64_t nblocks, uint32_t* out, uint64_t out_bs, hipStream_t stream) {
     if (!nblocks || !nrows || S == 0) return RSMI_OK;  // R(empty) = 0
     int rc = ensure_crc32_tables(c);
     if (rc) return rc;
-    const bool aligned = reinterpret_cast<uintptr_t>(base) % 16 == 0 && rpitch % 16 == 0 && bstride % 16 == 0;
+    const bool aligned = rows_aligned(base, rpitch, bstride);
     const bool mfma = c->opt_crc32_fold == 1;
     void* fn = mfma ? crc32_rows_mfma_kernel(aligned) : crc32_rows_kernel(aligned);
-    const uint64_t tile = uint64_t(kWave) * 16, span = tile * kCrc32SegTiles;
-    if (S / span >= (uint64_t(1) << kCrc32SegPowers)) return RSMI_ERR_INVALID_ARG;  // rows below 4 GiB
-    // unaligned rows fold on the memory's 16-byte grid, where a row spans its misalignment + S bytes
-    uint32_t tpb = uint32_t((S + (aligned ? 0 : 15) + tile - 1) / tile);
-    uint32_t nseg = (tpb + kCrc32SegTiles - 1) / kCrc32SegTiles;
-    uint32_t nsup = (nseg + kCrc32SupGroups - 1) / kCrc32SupGroups;
+    const uint64_t seg = uint64_t(kWave) * 16 * kCrc32SegTiles;
+    if (S / seg >= (uint64_t(1) << kCrc32SegPowers)) return RSMI_ERR_INVALID_ARG;  // rows below 4 GiB
+    // unaligned rows fold on the memory's 16-byte grid, where a row spans its misalignment + S bytes.
+    // 96 waves per CU as for the CRC-16 pass; the matrix-core pass: workgroups of 8 waves, 2
+    // resident per CU by its 66 KiB of LDS, each staging the 64 KiB of weights: 48 waves per CU,
+    // three rounds, measured best of 16-96 (profiles/r03/crc/crc32_mfma_wpc.txt)
+    const uint64_t wpg = mfma ? uint64_t(kCrc32MfmaWG) / kWave : kWG / kWave;
+    RowsGrid g = rows_grid(c, S + (aligned ? 0 : 15), nrows, nblocks, wpg, mfma && !kCrc32MfmaHalf ? 48 : 96);
     // the per-launch shift to the row's end (crc32.hpp), cached for the last S
     if (c->crc32_shift_S != S) {
-        crc32_tables().shift_columns(S % span, c->crc32_shift.col);
+        crc32_tables().shift_columns(S % seg, c->crc32_shift.col);
         c->crc32_shift_S = S;
     }
     Crc32Shift sh = c->crc32_shift;
-    uint64_t nitems = nblocks * nrows * nsup;
-    // 96 waves per CU as for the CRC-16 pass
-    // (the matrix-core pass: workgroups of 8 waves, 2 resident per CU by its 66 KiB of LDS, each
-    // staging the 64 KiB of weights: 48 waves per CU, three rounds, measured best of 16-96,
-    // profiles/r03/crc/crc32_mfma_wpc.txt)
-    const uint64_t wpg = mfma ? uint64_t(kCrc32MfmaWG) / kWave : 4;
-    uint64_t cap = uint64_t(c->num_cu) * (mfma && !kCrc32MfmaHalf ? 48 : 96) / wpg;
-    if (c->opt_waves_per_cu > 0) cap = std::max<uint64_t>(1, uint64_t(c->num_cu) * uint64_t(c->opt_waves_per_cu) / wpg);
-    const uint64_t wgs = std::min<uint64_t>((nitems + wpg - 1) / wpg, cap);
     const uint32_t* tb = c->d_crc32_tbl;
-    void* args[] = {&tb, &base, &bstride, &rpitch, &nrows, &S, &tpb, &nseg, &nsup, &nitems, &out, &out_bs, &sh};
-    HIP_TRY(hipLaunchKernel(fn, dim3(uint32_t(wgs)), dim3(uint32_t(wpg * kWave)), args, 0, stream));
+    void* args[] = {&tb, &base, &bstride, &rpitch, &nrows, &S, &g.tpb, &g.nsup, &g.nitems, &out, &out_bs, &sh};
+    HIP_TRY(hipLaunchKernel(fn, dim3(g.wgs), dim3(uint32_t(wpg * kWave)), args, 0, stream));
     return RSMI_OK;
 }
 
@@ -289,6 +302,29 @@ int launch_encode_crc(rsmi_ctx* c, const Plan& plan, const uint8_t* in, size_t i
     return launch_plan_crc(c, plan, in, in_rs, in_bs, out, out_rs, out_bs, S, nblocks, raw, st);
 }
 
+// What rsmi_crc16_rows_dev and rsmi_crc32_rows_dev share: the argument checks, the lock, the
+// device, then the caller's launch(stream) and, if it went through, its last_kernel label.
+struct RowsLaunched {
+    int rc;
+    const char* label;
+};
+template <class Launch>
+int rows_dev(rsmi_ctx* c, const uint8_t* d_rows, size_t shard_stride, int nrows, size_t S, uint32_t* d_raw_out,
+             size_t out_block_stride, void* stream, Launch&& launch) try {
+    if (!c || !d_rows || !d_raw_out || nrows < 0 || out_block_stride < size_t(nrows)) return RSMI_ERR_INVALID_ARG;
+    if (nrows > 1 && shard_stride < S) return RSMI_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    int rc = ensure_device(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const RowsLaunched r = launch(static_cast<hipStream_t>(stream));
+    if (r.rc) return r.rc;
+    set_last_kernel(c, r.label);
+    return hip_status(hipGetLastError());
+} catch (...) {
+    return exception_status();
+}
+
 }  // namespace impl
 }  // namespace rsmi
 
@@ -328,42 +364,29 @@ int rsmi_encode_batch_dev_crc(rsmi_ctx* c, const uint8_t* d_data, size_t data_sh
 }
 
 int rsmi_crc16_rows_dev(rsmi_ctx* c, const uint8_t* d_rows, size_t shard_stride, size_t block_stride, int nrows,
-                        size_t S, size_t nblocks, uint32_t* d_raw_out, size_t out_block_stride, void* stream) try {
-    if (!c || !d_rows || !d_raw_out || nrows < 0 || out_block_stride < size_t(nrows)) return RSMI_ERR_INVALID_ARG;
-    if (nrows > 1 && shard_stride < S) return RSMI_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(c->mu);
-    int rc = ensure_device(c);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    rc = launch_crc(c, d_rows, shard_stride, block_stride, uint32_t(nrows), S, nblocks, d_raw_out, out_block_stride,
-                    static_cast<hipStream_t>(stream));
-    if (rc) return rc;
-    const bool aligned = reinterpret_cast<uintptr_t>(d_rows) % 16 == 0 && shard_stride % 16 == 0 && block_stride % 16 == 0;
-    set_last_kernel(c, c->opt_crc16_fold == 1 ? (aligned ? "rs_crc16_rows_kernel,MFMA" : "rs_crc16_rows_kernel,MFMA,UA")
-                                              : "rs_crc16_rows_kernel");
-    return hip_status(hipGetLastError());
-} catch (...) {
-    return rsmi::impl::exception_status();
+                        size_t S, size_t nblocks, uint32_t* d_raw_out, size_t out_block_stride, void* stream) {
+    return rows_dev(c, d_rows, shard_stride, nrows, S, d_raw_out, out_block_stride, stream, [&](hipStream_t st) {
+        int rc = launch_crc(c, d_rows, shard_stride, block_stride, uint32_t(nrows), S, nblocks, d_raw_out,
+                            out_block_stride, st);
+        const bool aligned = rows_aligned(d_rows, shard_stride, block_stride);
+        return RowsLaunched{rc, c->opt_crc16_fold != 1 ? "rs_crc16_rows_kernel"
+                                : aligned              ? "rs_crc16_rows_kernel,MFMA"
+                                                       : "rs_crc16_rows_kernel,MFMA,UA"};
+    });
 }
 
 int rsmi_crc32_rows_dev(rsmi_ctx* c, const uint8_t* d_rows, size_t shard_stride, size_t block_stride, int nrows,
-                        size_t S, size_t nblocks, uint32_t* d_raw_out, size_t out_block_stride, void* stream) try {
-    if (!c || !d_rows || !d_raw_out || nrows < 0 || out_block_stride < size_t(nrows)) return RSMI_ERR_INVALID_ARG;
-    if (nrows > 1 && shard_stride < S) return RSMI_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(c->mu);
-    int rc = ensure_device(c);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (nblocks && nrows)
-        HIP_TRY(hipMemset2DAsync(d_raw_out, out_block_stride * 4, 0, size_t(nrows) * 4, nblocks, st));
-    rc = launch_crc32(c, d_rows, shard_stride, block_stride, uint32_t(nrows), S, nblocks, d_raw_out, out_block_stride,
-                      st);
-    if (rc) return rc;
-    set_last_kernel(c, c->opt_crc32_fold == 1 ? "rs_crc32_rows_kernel,MFMA" : "rs_crc32_rows_kernel");
-    return hip_status(hipGetLastError());
-} catch (...) {
-    return rsmi::impl::exception_status();
+                        size_t S, size_t nblocks, uint32_t* d_raw_out, size_t out_block_stride, void* stream) {
+    return rows_dev(c, d_rows, shard_stride, nrows, S, d_raw_out, out_block_stride, stream, [&](hipStream_t st) {
+        const char* label = c->opt_crc32_fold == 1 ? "rs_crc32_rows_kernel,MFMA" : "rs_crc32_rows_kernel";
+        if (nblocks && nrows) {  // launch_crc32 adds into the words
+            int rc = hip_status(hipMemset2DAsync(d_raw_out, out_block_stride * 4, 0, size_t(nrows) * 4, nblocks, st));
+            if (rc) return RowsLaunched{rc, label};
+        }
+        return RowsLaunched{launch_crc32(c, d_rows, shard_stride, block_stride, uint32_t(nrows), S, nblocks, d_raw_out,
+                                         out_block_stride, st),
+                            label};
+    });
 }
 
 int rsmi_crc_rows_host(rsmi_ctx* c, const uint8_t* rows, size_t row_stride, size_t nrows, size_t S,

@@ -13,7 +13,8 @@
 // No CPU compute path anywhere: every byte of parity, reconstructed data or CRC and every verify
 // flag comes out of the HIP kernels (rs_kernels.hip, rs_kernels_tb.hip, rs_crc16_kernels.hip, rs_crc32_kernels.hip,
 // rs_verify_kernels.hip, rs_locate_kernels.hip, rs_heal_kernels.hip, rs_mixed_kernels.hip,
-// rs_pair_kernels.hip).
+// rs_pair_kernels.hip).  Kernel headers: rs_gf_tile.hpp (the GF(2^8) tile pipeline), rs_verify_tile.hpp
+// (the stripe checks' tile step), rs_crc_rows.hpp (what the CRC-16 and CRC-32 rows passes share).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -170,7 +171,7 @@ struct rsmi_ctx {
     CrcScratch own_scratch;  // the fused encode + CRC-16's scratch on the context's own streams
     std::map<hipStream_t, CrcScratch> stream_scratch;  // ... and on each caller stream (device-resident calls)
     // options
-    int opt_crc16_fold = 1;     // aligned CRC-16 rows pass: 0 = nibble tables, 1 = matrix cores (fp4)
+    int opt_crc16_fold = 1;     // CRC-16 rows pass, either layout: 0 = nibble tables, 1 = matrix cores (fp4)
     int opt_crc32_fold = RSMI_CRC32_FOLD_DEFAULT;  // CRC-32 rows pass: 0 = nibble tables, 1 = matrix cores
     int opt_fused_fold = 1;     // aligned fused encode + CRC-16: 0 = nibble tables, 1 = matrix cores (fp4)
     long opt_waves_per_cu = 0;  // grid cap (0 = one tile per wave / the CRC passes' defaults)

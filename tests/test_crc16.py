@@ -95,8 +95,8 @@ def _device_rows(nb, nrows, S, pitch, offset, seed):
 @pytest.mark.parametrize("wpc", [0, 1])
 @pytest.mark.parametrize("fold", [1, 0])
 def test_rows_dev_matches_oracle(S, layout, wpc, fold):
-    """Fold 1 (the default) runs the matrix-core pass -- on unaligned rows with aligned loads
-    funnel-shifted by the row's misalignment --, fold 0 the nibble passes (pipelined on aligned
+    """Fold 1 (the default) runs the matrix-core pass -- on unaligned rows folded on the memory's
+    16-byte grid, aligned loads only --, fold 0 the nibble passes (pipelined on aligned
     rows); waves_per_cu=1 makes each wave walk many items (the pipelined pass's two register sets
     alternate).  Row sizes cover half-group, group (8 KiB) and item (32 KiB) boundaries on both
     sides; unaligned rows sit at pitch S + 3 from offset 5, so their misalignments vary."""
