@@ -220,6 +220,20 @@ constexpr int pair_blocks(int K, int MT) { return (pair_tests(K) * (MT - 2) + 3)
 constexpr int pair_bit(int n, int x, int y) { return x * n - x * (x + 1) / 2 + (y - x - 1); }
 constexpr int pair_words(int n) { return (n * (n - 1) / 2 + 31) / 32; }
 
+// rsmi_heal_pair (rs_heal_pair_kernels.hip): rs_heal_pair_kernel per (K, MT = m), the shapes of
+// rs_locate_pair_kernel, and the byte-granular kernel of the fallback.  Plan "H" (rsmi_heal_pair.cpp)
+// has one column per explanation of a block: the C(n, 2) pairs {x, y} at pair_bit(n, x, y), then the n
+// single shards.  Column e carries D's four coefficients in its output slots (D[0][l0], D[0][l1],
+// D[1][l0], D[1][l1]) and l0 | l1 << 8 in in_row[e].
+struct HealPairKernelTable {
+    void* fn[17][kMaxMT + 1];
+    void* ua[17][kMaxMT + 1];
+};
+const HealPairKernelTable& heal_pair_kernels();
+void* heal_pair_rows_kernel();
+constexpr int heal_pair_entries(int n) { return n * (n - 1) / 2 + n; }
+constexpr int heal_pair_entry(int n, int x, int y) { return y < 0 ? n * (n - 1) / 2 + x : pair_bit(n, x, y); }
+
 // rsmi_reconstruct_mixed_batch_* (rs_mixed_kernels.hip): rs_mixed_kernel per (K, MT), the K of
 // the verify kernels, aligned and unaligned-window layouts (null when the shape has none).  A
 // launch codes the tiles of one class of blocks: entry e of its list names the block and, through

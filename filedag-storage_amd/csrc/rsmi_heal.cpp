@@ -14,21 +14,14 @@ using namespace rsmi::impl;
 namespace rsmi {
 namespace impl {
 
-namespace {
-
-// Heal of nblocks blocks (caller holds ctx->mu, the device is bound): launch_locate's outputs,
-// then the heal launch, stream-ordered.  culprit is the caller's verdicts and the heal kernel's
-// input at once.
-int launch_heal(rsmi_ctx* c, const Plan& plan, uint8_t* data, uint64_t data_rs, uint64_t data_bs, uint8_t* parity,
-                uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks, int32_t* culprit, uint32_t* bad,
-                hipStream_t stream) {
-    if (nblocks == 0 || S == 0) return RSMI_OK;
-    StripeLayout fused = StripeLayout::kNeither;
-    int rc = launch_locate(c, plan, data, data_rs, data_bs, parity, parity_rs, parity_bs, S, nblocks, culprit, bad,
-                           stream, &fused);
-    if (rc) return rc;
-    // every shard explains any damage: nothing is ever named, the launches were Verify's
-    if (c->m == 1) return RSMI_OK;
+// The heal launch behind launch_locate's verdicts (caller holds ctx->mu, the device is bound; m >= 2):
+// the named row of every block whose verdict culprit[b] names one, rewritten.  fused: the layout
+// launch_locate reports.  rsmi_heal_pair (rsmi_heal_pair.cpp) runs it for m = 2, where no pair is
+// ever named.
+int launch_heal_named(rsmi_ctx* c, const Plan& plan, StripeLayout fused, uint8_t* data, uint64_t data_rs,
+                      uint64_t data_bs, uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S,
+                      uint64_t nblocks, int32_t* culprit, hipStream_t stream) {
+    int rc = RSMI_OK;
     if (fused != StripeLayout::kNeither) {
         // the heal kernel of the layout rs_locate_kernel ran on
         const bool aligned = fused == StripeLayout::kAligned;
@@ -68,6 +61,25 @@ int launch_heal(rsmi_ctx* c, const Plan& plan, uint8_t* data, uint64_t data_rs, 
     if (rc) return rc;
     set_last_kernel(c, "rs_heal_rows_kernel");
     return hip_status(hipGetLastError());
+}
+
+namespace {
+
+// Heal of nblocks blocks (caller holds ctx->mu, the device is bound): launch_locate's outputs,
+// then the heal launch, stream-ordered.  culprit is the caller's verdicts and the heal kernel's
+// input at once.
+int launch_heal(rsmi_ctx* c, const Plan& plan, uint8_t* data, uint64_t data_rs, uint64_t data_bs, uint8_t* parity,
+                uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks, int32_t* culprit, uint32_t* bad,
+                hipStream_t stream) {
+    if (nblocks == 0 || S == 0) return RSMI_OK;
+    StripeLayout fused = StripeLayout::kNeither;
+    int rc = launch_locate(c, plan, data, data_rs, data_bs, parity, parity_rs, parity_bs, S, nblocks, culprit, bad,
+                           stream, &fused);
+    if (rc) return rc;
+    // every shard explains any damage: nothing is ever named, the launches were Verify's
+    if (c->m == 1) return RSMI_OK;
+    return launch_heal_named(c, plan, fused, data, data_rs, data_bs, parity, parity_rs, parity_bs, S, nblocks, culprit,
+                             stream);
 }
 
 // Host-memory heal on Verify's host paths: locate_host_impl's buffers, and the write-back leg.

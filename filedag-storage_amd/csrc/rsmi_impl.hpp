@@ -10,10 +10,11 @@
 //   rsmi_heal.cpp      rsmi_heal: locate, then the named shard rewritten on the same stream
 //   rsmi_mixed.cpp     rsmi_reconstruct_mixed_*: a batch whose blocks each have their own erasure pattern
 //   rsmi_pair.cpp      rsmi_locate_pair: locate, then the pair of shards that explains an UNKNOWN block
+//   rsmi_heal_pair.cpp rsmi_heal_pair: locate pair, then the one or two named shards rewritten on the same stream
 // No CPU compute path anywhere: every byte of parity, reconstructed data or CRC and every verify
 // flag comes out of the HIP kernels (rs_kernels.hip, rs_kernels_tb.hip, rs_crc16_kernels.hip, rs_crc32_kernels.hip,
 // rs_verify_kernels.hip, rs_locate_kernels.hip, rs_heal_kernels.hip, rs_mixed_kernels.hip,
-// rs_pair_kernels.hip).  Kernel headers: rs_gf_tile.hpp (the GF(2^8) tile pipeline), rs_verify_tile.hpp
+// rs_pair_kernels.hip, rs_heal_pair_kernels.hip).  Kernel headers: rs_gf_tile.hpp (the GF(2^8) tile pipeline), rs_verify_tile.hpp
 // (the stripe checks' tile step), rs_crc_rows.hpp (what the CRC-16 and CRC-32 rows passes share).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -336,7 +337,8 @@ int begin_stripe_dev_call(rsmi_ctx* c, std::unique_lock<std::mutex>& lock, std::
 //   launch()   per staged range of nb blocks from block b0, rows visible to the device
 //   fetch(st)  the results to the caller's memory: queued on st, which the caller then
 //              synchronises, or (st null, every stream idle) copied synchronously
-// rsmi_heal alone writes rows, so it alone sets the write-back leg (unset: no step is added):
+// rsmi_heal and rsmi_heal_pair alone write rows, so they alone set the write-back leg (unset: no
+// step is added):
 //   small_done(sd, sp)          the small staged call, after its synchronisation: the page-locked
 //                               copies of the data blocks (k*S apart) and of the parity blocks
 //                               (m*S apart), null for a half that was not staged
@@ -368,6 +370,22 @@ void stripe_results(rsmi_ctx* c, size_t nblocks, int32_t* culprit_out, uint32_t*
 int launch_locate(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
                   const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks,
                   int32_t* culprit, uint32_t* bad, hipStream_t stream, StripeLayout* fused = nullptr);
+// rsmi_heal's launch behind launch_locate's verdicts (rsmi_heal.cpp; caller holds ctx->mu, m >= 2):
+// rs_heal_kernel on the layout fused names, or the encode into scratch and rs_heal_rows_kernel.
+int launch_heal_named(rsmi_ctx* c, const Plan& plan, StripeLayout fused, uint8_t* data, uint64_t data_rs,
+                      uint64_t data_bs, uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S,
+                      uint64_t nblocks, int32_t* culprit, hipStream_t stream);
+// rsmi_locate_pair of nblocks blocks (rsmi_pair.cpp; caller holds ctx->mu): two verdict words per
+// block in out and, when bad is given, Verify's flags, device memory, stream-ordered.  info: the
+// layout rs_locate_kernel ran on (kNeither: the fallback) and rsmi_locate's verdicts, one word per
+// block in the stream's scratch, valid until the stream's next stripe call.
+struct PairLaunch {
+    StripeLayout fused = StripeLayout::kNeither;
+    int32_t* culprit = nullptr;
+};
+int launch_locate_pair(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
+                       const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks,
+                       int32_t* out, uint32_t* bad, hipStream_t stream, PairLaunch* info = nullptr);
 // the ratio matrix's plan "L" (output slot 0: inv(M[k][c])) and the byte-granular kernels' tables
 // (ctx->d_locate_tbl: log | exp | R | inv(M[k][c])), both built on first use
 int ratio_plan(rsmi_ctx* c, std::shared_ptr<Plan>& out);

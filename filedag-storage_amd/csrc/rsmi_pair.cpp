@@ -109,13 +109,17 @@ int launch_pair_verdict(const int32_t* culprit, const uint32_t* pairw, uint32_t 
     return RSMI_OK;
 }
 
+}  // namespace
+
 // Pair locate of nblocks blocks (caller holds ctx->mu, the device is bound): out[2b], out[2b+1]
 // and, when bad is given, Verify's flags, device memory.  Stream-ordered.  The stream's
 // locate_scratch holds, behind launch_locate's candidate words, rsmi_locate's verdicts, the pair
-// words and (when the caller takes none) the flags.
+// words and (when the caller takes none) the flags.  info (rsmi_heal_pair.cpp): the layout
+// rs_locate_kernel ran on and where rsmi_locate's verdicts lie.
 int launch_locate_pair(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
                        const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks,
-                       int32_t* out, uint32_t* bad, hipStream_t stream) {
+                       int32_t* out, uint32_t* bad, hipStream_t stream, PairLaunch* info) {
+    if (info) *info = PairLaunch{};
     if (nblocks == 0 || S == 0) return RSMI_OK;
     const uint64_t m = uint64_t(c->m);
     const uint32_t n32 = uint32_t(c->n);
@@ -137,6 +141,10 @@ int launch_locate_pair(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint6
     rc = launch_locate(c, plan, data, data_rs, data_bs, parity, parity_rs, parity_bs, S, nblocks, culprit, bad, stream,
                        &fused);
     if (rc) return rc;
+    if (info) {
+        info->fused = fused;
+        info->culprit = culprit;
+    }
     // every pair explains everything: rsmi_locate's verdicts, widened
     if (c->m <= 2) {
         if ((rc = launch_pair_verdict(culprit, nullptr, n32, 0, nblocks, out, stream))) return rc;
@@ -189,6 +197,8 @@ int launch_locate_pair(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint6
     set_last_kernel(c, "rs_locate_pair_rows_kernel");
     return hip_status(hipGetLastError());
 }
+
+namespace {
 
 // Host-memory pair locate on Verify's host paths (verify_host_impl).  Launch and read-back are
 // this call's own: the context's device result buffer holds the flags, then two verdict words per

@@ -115,6 +115,12 @@ def lib() -> ctypes.CDLL:
         "rsmi_heal_batch_host": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, u8p, c_size, c_size, c_size,
                                                 ctypes.c_void_p, ctypes.c_void_p]),
         "rsmi_heal": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, ctypes.POINTER(ctypes.c_int)]),
+        "rsmi_heal_pair_batch_dev": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, u8p, c_size, c_size, c_size,
+                                                    c_size, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+        "rsmi_heal_pair_batch_host": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, u8p, c_size, c_size, c_size,
+                                                     ctypes.c_void_p, ctypes.c_void_p]),
+        "rsmi_heal_pair": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, ctypes.POINTER(ctypes.c_int)]),
+        "rsmi_heal_pair_matrix": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, u8p]),
         "rsmi_encode_block_coalesced": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, u8p, ctypes.c_void_p]),
         "rsmi_encode_block_coalesced_crcs": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, u8p, ctypes.c_void_p,
                                                             ctypes.c_void_p]),
@@ -259,6 +265,13 @@ class Codec:
         _check(lib().rsmi_locate_pair_checks(self._h, x, y, ctypes.addressof(_buf(scratch))))
         return bytes(out)
 
+    def heal_pair_matrix(self, x: int, y: int) -> bytes:
+        """rsmi_heal_pair_matrix: the 2 x m matrix D, row-major, with D h_x = (1, 0) and D h_y = (0, 1) for
+        the columns of H = [M | I]; D syn is (row x's error, row y's error) where {x, y} explains."""
+        out = bytearray(2 * self.m)
+        _check(lib().rsmi_heal_pair_matrix(self._h, x, y, ctypes.addressof(_buf(out))))
+        return bytes(out)
+
     def set_option(self, key: str, value: int) -> None:
         _check(lib().rsmi_set_option(self._h, key.encode(), int(value)))
 
@@ -350,6 +363,23 @@ class Codec:
         that has one rewritten in the caller's buffers."""
         _check(lib().rsmi_heal_batch_host(self._h, data_ptr, data_bs, parity_ptr, parity_bs, S, nblocks,
                                           culprit_ptr, bad_ptr or None))
+
+    def heal_pair(self, shards: bytearray, S: int) -> Tuple[int, int]:
+        """rsmi_heal_pair of one block of n*S contiguous bytes, healed in place: the verdict of the
+        block as it was (rsmi_locate_pair's); the one or two rows it names are rewritten so that
+        the stripe is clean, and nothing else is."""
+        if not isinstance(shards, bytearray):
+            raise TypeError("heal_pair rewrites its argument: pass a bytearray")
+        v = (ctypes.c_int * 2)(LocateUnknown, LocateUnknown)
+        _check(lib().rsmi_heal_pair(self._h, ctypes.addressof(_buf(shards)) if shards else None, S, v))
+        return v[0], v[1]
+
+    def heal_pair_batch_host_ptr(self, data_ptr: int, data_bs: int, parity_ptr: int, parity_bs: int, S: int,
+                                 nblocks: int, pair_ptr: int, bad_ptr: int = 0) -> None:
+        """rsmi_heal_pair_batch_host: rsmi_locate_pair_batch_host's outputs, and the one or two named
+        rows of every block that has any rewritten in the caller's buffers."""
+        _check(lib().rsmi_heal_pair_batch_host(self._h, data_ptr, data_bs, parity_ptr, parity_bs, S, nblocks,
+                                               pair_ptr, bad_ptr or None))
 
     def reconstruct_batch_host_ptr(self, ptr: int, bs: int, S: int, nblocks: int, present: Sequence[bool],
                                    data_only: bool) -> None:
@@ -475,6 +505,14 @@ class Codec:
         the named row of every block that has one rewritten so that the stripe is clean."""
         _check(lib().rsmi_heal_batch_dev(self._h, d_data, data_rs, data_bs, d_parity, parity_rs, parity_bs, S,
                                          nblocks, d_culprit, d_bad or None, stream or None))
+
+    def heal_pair_batch_dev(self, d_data: int, data_rs: int, data_bs: int, d_parity: int, parity_rs: int,
+                            parity_bs: int, S: int, nblocks: int, d_pair: int, d_bad: int = 0, stream: int = 0) -> None:
+        """rsmi_heal_pair_batch_dev: rsmi_locate_pair_batch_dev's outputs, then, behind them on the
+        stream, the one or two named rows of every block that has any rewritten so that the stripe is
+        clean."""
+        _check(lib().rsmi_heal_pair_batch_dev(self._h, d_data, data_rs, data_bs, d_parity, parity_rs, parity_bs, S,
+                                              nblocks, d_pair, d_bad or None, stream or None))
 
     def reconstruct_rows_batch_dev(self, d_shards: int, rs: int, bs: int, S: int, nblocks: int,
                                    present: Sequence[bool], required: Sequence[bool], stream: int = 0) -> None:
@@ -821,6 +859,24 @@ class Erasure:
         out = list(shards)
         if v >= 0:
             out[v] = bytes(buf[v * S:(v + 1) * S])
+        return v, out
+
+    def heal_pair(self, shards: List[bytes]) -> Tuple[Tuple[int, int], List[bytes]]:
+        """Locate singles and pairs, then rewrite the named shards (rsmi_heal_pair): ((x, y), shards),
+        the verdict that of locate_pair for the list as given; the entries it names are their
+        reconstruction from the others, every other entry is the caller's.  The shard list is
+        checked as verify checks it."""
+        n = self.data_blocks + self.parity_blocks
+        if len(shards) != n:
+            raise RsmiError(ErrTooFewShards)
+        rc, S = check_shards([len(s) if s else 0 for s in shards], nil_ok=False)
+        _check(rc)
+        buf = bytearray(b"".join(shards))
+        v = self.encoder().heal_pair(buf, S)
+        out = list(shards)
+        for x in v:
+            if x >= 0:
+                out[x] = bytes(buf[x * S:(x + 1) * S])
         return v, out
 
 

@@ -39,9 +39,10 @@ extern "C" {
  * so did the locate entry points (rsmi_locate, rsmi_locate_batch_host, rsmi_locate_batch_dev,
  * rsmi_locate_matrix), the heal entry points (rsmi_heal, rsmi_heal_batch_host,
  * rsmi_heal_batch_dev), the mixed-batch reconstruct (rsmi_reconstruct_mixed_batch_dev,
- * rsmi_reconstruct_mixed_batch_host, rsmi_reconstruct_mixed_classify) and the pair locate
+ * rsmi_reconstruct_mixed_batch_host, rsmi_reconstruct_mixed_classify), the pair locate
  * (rsmi_locate_pair, rsmi_locate_pair_batch_host, rsmi_locate_pair_batch_dev,
- * rsmi_locate_pair_checks). */
+ * rsmi_locate_pair_checks) and the pair heal (rsmi_heal_pair, rsmi_heal_pair_batch_host,
+ * rsmi_heal_pair_batch_dev, rsmi_heal_pair_matrix). */
 #define RSMI_ABI_VERSION 5
 
 typedef struct rsmi_ctx rsmi_ctx;
@@ -391,6 +392,65 @@ int rsmi_heal_batch_host(rsmi_ctx* ctx, uint8_t* data, size_t data_block_stride,
 
 /* One block of n*S contiguous bytes, healed in place: *culprit_out receives its verdict. */
 int rsmi_heal(rsmi_ctx* ctx, uint8_t* shards, size_t S, int* culprit_out);
+
+/* ------------------------------------------------------------------ heal pair: rewrite the two shards that are wrong */
+
+/* Locate pair names the two shards that break a stripe; heal pair goes on, on the same stream and
+ * with no host round trip in between, to rewrite them.  One call locates singles and pairs and
+ * rewrites every named shard; every dirty block may have its own pair.  Blocks that come back
+ * (-2, -2) are untouched and go to the caller's slow path.
+ *   Outputs.  pair_out and the optional bad_out are exactly what rsmi_locate_pair_* returns for the
+ *   stripes as they were before the call.
+ *   What is written.  Verdict (x, -1): bytes [0, S) of row x are rewritten exactly as rsmi_heal
+ *   rewrites them.  Verdict (x, y): bytes [0, S) of rows x and y are rewritten to their
+ *   reconstruction from the other n - 2 rows, so the stripe is clean.  Blocks with (-1, -1) or
+ *   (-2, -2) are not written at all.  No other row is written, no byte at or past S of any row, no
+ *   byte of a gap: the layout contract holds, padding may be read and is never written.
+ *   What the code's distance (m + 1) gives -- a property of the code, not of the implementation:
+ *     m <= 2   the call is rsmi_heal with its verdicts widened to two words;
+ *     m = 3    a pair is healed when it is the block's only explanation; that is not guaranteed;
+ *     m >= 4   two damaged shards get their original bytes back;
+ *   with three or more damaged shards the damage can imitate a pair; the heal then makes a clean
+ *   codeword that is not the original.  Callers that cannot bound the damage keep the shard
+ *   checksums as the second witness.
+ *   Overlap.  The data and parity halves must not overlap each other.
+ * Layout, argument checks, their order and their statuses are those of rsmi_locate_pair_*; the
+ * shards are writable, as in rsmi_heal_*.  The calls are joined to ABI version 5 (additive); none
+ * of them takes or clears the per-thread wait hook. */
+
+/* Device-resident.  Stream-ordered, no sync: d_pair_out is written by the locate pair launches and
+ * read by the heal launch behind them on the stream (scratch is kept per stream; growing it waits
+ * for that stream once). */
+int rsmi_heal_pair_batch_dev(rsmi_ctx* ctx, uint8_t* d_data, size_t data_shard_stride, size_t data_block_stride,
+                             uint8_t* d_parity, size_t parity_shard_stride, size_t parity_block_stride, size_t S,
+                             size_t nblocks, int32_t* d_pair_out, uint32_t* d_bad_out, void* stream);
+
+/* Host memory, layout and the three paths of rsmi_verify_batch_host; pair_out[2b], pair_out[2b+1]
+ * and (when not NULL) bad_out[b*m + j] in host memory.  Page-locked data and parity are healed
+ * where they lie; from the staging of a small call and from the device rows of the upload pipeline
+ * the one or two rewritten rows of a block are copied back to the caller's buffers, and nothing
+ * else. */
+int rsmi_heal_pair_batch_host(rsmi_ctx* ctx, uint8_t* data, size_t data_block_stride, uint8_t* parity,
+                              size_t parity_block_stride, size_t S, size_t nblocks, int32_t* pair_out,
+                              uint32_t* bad_out);
+
+/* One block of n*S contiguous bytes, healed in place: pair_out[0], pair_out[1] receive its verdict. */
+int rsmi_heal_pair(rsmi_ctx* ctx, uint8_t* shards, size_t S, int pair_out[2]);
+
+/* Host-only, works without a GPU: the 2 x m matrix D (row-major in out) with D h_x = (1, 0)^T and
+ * D h_y = (0, 1)^T for the columns of H = [M | I_m].  With syn Verify's syndrome vector, D syn is
+ * (row x's error, row y's error) at every byte column that {x, y} explains.  D is the form the
+ * kernels use, with at most two non-zero columns l0, l1:
+ *   {k+i, k+j}   the unit rows i, j;
+ *   {c, k+j}     l = 0 (1 when j = 0): e_c = syn_l / M[l][c], e_{k+j} = syn_j ^ M[j][c] e_c;
+ *   {c, d}       the inverse of the 2 x 2 minor of rows 0, 1 (non-singular for every pair: M is MDS).
+ * D [h_x h_y] = I_2 is what makes the kernels' update idempotent per byte.  On layouts whose rows
+ * are not 16-byte aligned a row's last 16-byte window overlaps the one before it, and the two may
+ * be healed by different waves: a wave that sees row x healed already and row y not forms
+ * syn = h_y e_y and gets the deltas (0, e_y).  That holds because each byte's deltas come from the
+ * same loads as its syndromes: no byte is loaded twice.
+ * x == y, an index outside [0, n) or m < 2: RSMI_ERR_INVALID_ARG. */
+int rsmi_heal_pair_matrix(const rsmi_ctx* ctx, int x, int y, uint8_t* out);
 
 /* Erasure.EncodeData for one block (same output as rsmi_encode_block, plus R(shard) in
  * raw_out[0..k+m) when raw_out is not NULL), coalesced with concurrent callers on the same
