@@ -95,6 +95,7 @@ __device__ __forceinline__ void heal_pair_tiles(u32x4* s_tbl, const RsPlanDev* _
                 if (uint32_t(c) == yr) oldy = x;
                 asm volatile("" : "+v"(oldx), "+v"(oldy));
             },
+            GfNone{}, GfNone{},
             [&](int j, const uint32_t(&s)[4], const u32x4& sp) {
                 if (xr == uint32_t(K + j)) oldx = sp;
                 if (yr == uint32_t(K + j)) oldy = sp;

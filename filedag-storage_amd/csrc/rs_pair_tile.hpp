@@ -181,7 +181,7 @@ __device__ __forceinline__ void pair_tiles(u32x4* s_tbl, const RsPlanDev* __rest
         uint32_t syn[MT][4];
         uint64_t dirty = 0;  // the lanes that saw a non-zero syndrome (wave-uniform)
         stripe_tile<K, MT, UA>(s_tbl, in + uint64_t(blk) * in_bs, par + uint64_t(blk) * par_bs, in_off, par_off,
-                               lane_chunk<UA>(tw.tib, lane, cpb, S), cpb, S, GfNone{},
+                               lane_chunk<UA>(tw.tib, lane, cpb, S), cpb, S, GfNone{}, GfNone{}, GfNone{},
                                [&](int j, const uint32_t(&s)[4], const u32x4&) {
                                    uint32_t d = 0;
 #pragma unroll

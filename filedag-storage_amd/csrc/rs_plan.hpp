@@ -181,6 +181,15 @@ struct VerifyKernelTable {
 const VerifyKernelTable& verify_kernels();
 void* compare_rows_kernel();
 
+// rsmi_scrub (rs_scrub_kernels.hip): rs_scrub_mfma_kernel per (K, MT), the shapes of
+// rs_verify_kernel, aligned and unaligned-window layouts (null: Verify and the CRC-16 rows pass,
+// one after the other)
+struct ScrubKernelTable {
+    void* fn[17][kMaxMT + 1];
+    void* ua[17][kMaxMT + 1];
+};
+const ScrubKernelTable& scrub_kernels();
+
 // rsmi_locate (rs_locate_kernels.hip): rs_locate_kernel per (K, MT = m), m = 2..4, aligned and
 // unaligned-window layouts (null when the shape has none), the verdict kernel that follows every
 // locate launch, and the byte-granular kernel of the fallback

@@ -1,7 +1,9 @@
 // rs_verify_tile.hpp -- the stripe checks' tile pipeline: one step, stripe_tile, and its two
-// consumers.  stripe_tile runs the coding kernels' GF(2^8) pipeline over one tile of the encode
-// plan, loads the stored parity chunks where the encode would store, and hands its caller, per
-// parity row j, the lane's masked syndrome
+// consumers here (a third, rs_scrub_mfma_kernel, rs_scrub_kernels.hip, also folds every chunk the
+// step loads into CRC-16 counts through the step's per-dword and per-column hooks).  stripe_tile
+// runs the coding kernels' GF(2^8) pipeline over one tile of the encode plan, loads the stored
+// parity chunks where the encode would store, and hands its caller, per parity row j, the lane's
+// masked syndrome
 //   syn_j = encode(data)_j ^ stored parity_j
 // and the stored chunk as loaded.  verify_tiles (rs_verify_kernel, rs_verify_kernels.hip;
 // rs_locate_kernel, rs_locate_kernels.hip) raises bad[block * m + parity row] where a syndrome is
@@ -69,13 +71,15 @@ __device__ __forceinline__ void row_offsets(const RsPlanDev* plan, uint64_t in_r
 // slots than parity rows (K < MT) the rest are loaded ahead of the column loop, so no load waits
 // behind the GF work.  Every load is nontemporal: nothing is read twice.
 //   before_col(c, x)       gf_tile_columns': data row c's chunk x as loaded, before its GF work
+//   after_dword(c, w, x)   gf_tile_columns': after the GF work of x's dword w
+//   after_col(c, x)        gf_tile_columns': after column c's GF work, before its slot is refilled
 //   on_row(j, syn, sp)     parity row j (a constant once unrolled): the syndrome's four dwords,
 //                          masked to the bytes of the lane's chunk that count, and the stored chunk
-template <int K, int MT, bool UA, class BeforeCol, class OnRow>
+template <int K, int MT, bool UA, class BeforeCol, class AfterDword, class AfterCol, class OnRow>
 __device__ __forceinline__ void stripe_tile(const u32x4* s_tbl, const uint8_t* ib, const uint8_t* pb,
                                             const uint64_t (&in_off)[K], const uint64_t (&par_off)[MT],
                                             const LaneChunk& lc, uint32_t cpb, uint32_t S, BeforeCol&& before_col,
-                                            OnRow&& on_row) {
+                                            AfterDword&& after_dword, AfterCol&& after_col, OnRow&& on_row) {
     constexpr int P = rows_in_flight<K, MT>();
     constexpr int PR = MT < P ? MT : P;  // parity rows that go through the ring
     // the bytes of the lane's chunk that count: none for a lane past the row's last chunk; UA:
@@ -104,7 +108,7 @@ __device__ __forceinline__ void stripe_tile(const u32x4* s_tbl, const uint8_t* i
 
     uint32_t acc[MT][4];
     // the freed slot takes the next input row or, once those are issued, parity row c + P - K
-    gf_tile_columns<K, MT, P>(s_tbl, v, acc, before_col, GfNone{}, GfNone{}, [&](int c, u32x4& x) {
+    gf_tile_columns<K, MT, P>(s_tbl, v, acc, before_col, after_dword, after_col, [&](int c, u32x4& x) {
         if (c + P < K)
             x = load_col(c + P);
         else if (c + P - K < PR)
@@ -192,7 +196,8 @@ __device__ __forceinline__ void verify_tiles(const u32x4* s_tbl, const RsPlanDev
         uint64_t dirty = 0;  // the lanes that saw a non-zero syndrome (wave-uniform)
         stripe_tile<K, MT, UA>(
             s_tbl, in + uint64_t(blk) * in_bs, par + uint64_t(blk) * par_bs, in_off, par_off,
-            lane_chunk<UA>(tw.tib, lane, cpb, S), cpb, S, GfNone{}, [&](int j, const uint32_t(&s)[4], const u32x4&) {
+            lane_chunk<UA>(tw.tib, lane, cpb, S), cpb, S, GfNone{}, GfNone{}, GfNone{},
+            [&](int j, const uint32_t(&s)[4], const u32x4&) {
                 uint32_t d = 0;
 #pragma unroll
                 for (int w = 0; w < 4; w++) {
@@ -278,6 +283,7 @@ __device__ __forceinline__ void heal_tiles(u32x4* s_tbl, const RsPlanDev* __rest
                 if (uint32_t(c) == xr) old = x;
                 asm volatile("" : "+v"(old));
             },
+            GfNone{}, GfNone{},
             [&](int j, const uint32_t(&s)[4], const u32x4& sp) {
                 if (j == 0) {
 #pragma unroll

@@ -463,6 +463,9 @@ void rsmi_close(rsmi_ctx* c) {
             for (auto& e : c->locate_scratch)
                 if (e.second.p) (void)hipFree(e.second.p);
             if (c->d_locate_tbl) (void)hipFree(c->d_locate_tbl);
+            if (!c->scrub_scratch.empty()) (void)hipDeviceSynchronize();
+            for (auto& e : c->scrub_scratch)
+                if (e.second.p) (void)hipFree(e.second.p);
             if (!c->mixed_scratch.empty()) (void)hipDeviceSynchronize();
             for (auto& e : c->mixed_scratch) {
                 if (e.second.d) (void)hipFree(e.second.d);

@@ -11,10 +11,11 @@
 //   rsmi_mixed.cpp     rsmi_reconstruct_mixed_*: a batch whose blocks each have their own erasure pattern
 //   rsmi_pair.cpp      rsmi_locate_pair: locate, then the pair of shards that explains an UNKNOWN block
 //   rsmi_heal_pair.cpp rsmi_heal_pair: locate pair, then the one or two named shards rewritten on the same stream
+//   rsmi_scrub.cpp     rsmi_scrub: Verify's flags and every shard's CRC-16 from one read of the rows
 // No CPU compute path anywhere: every byte of parity, reconstructed data or CRC and every verify
 // flag comes out of the HIP kernels (rs_kernels.hip, rs_kernels_tb.hip, rs_crc16_kernels.hip, rs_crc32_kernels.hip,
 // rs_verify_kernels.hip, rs_locate_kernels.hip, rs_heal_kernels.hip, rs_mixed_kernels.hip,
-// rs_pair_kernels.hip, rs_heal_pair_kernels.hip).  Kernel headers: rs_gf_tile.hpp (the GF(2^8) tile pipeline), rs_verify_tile.hpp
+// rs_pair_kernels.hip, rs_heal_pair_kernels.hip, rs_scrub_kernels.hip).  Kernel headers: rs_gf_tile.hpp (the GF(2^8) tile pipeline), rs_verify_tile.hpp
 // (the stripe checks' tile step), rs_crc_rows.hpp (what the CRC-16 and CRC-32 rows passes share).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -156,6 +157,8 @@ struct rsmi_ctx {
     // caller takes none) of its launches; the fallback kernel's tables, uploaded on first use
     std::map<hipStream_t, VerifyScratch> locate_scratch;
     uint8_t* d_locate_tbl = nullptr;
+    // rsmi_scrub (rsmi_scrub.cpp): per stream the unit records of rs_scrub_mfma_kernel
+    std::map<hipStream_t, VerifyScratch> scrub_scratch;
     // rsmi_reconstruct_mixed_batch_* (rsmi_mixed.cpp): per stream the class lists and plan
     // pointers of its launches.  A call's words are written to the page-locked half h at head and
     // copied from there to the same offset of the device half d, both on that stream; head moves
@@ -306,6 +309,14 @@ struct LocateFuse {
 int launch_verify(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
                   const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks,
                   uint32_t* bad, hipStream_t stream, LocateFuse* loc = nullptr);
+// rsmi_scrub of nblocks blocks (rsmi_scrub.cpp; caller holds ctx->mu): launch_verify's flags in
+// bad[b*m + j] and R(row) of every data and parity row over bytes [0, S) in raw[b*(k+m) + r], data
+// rows first, both device memory, from one read of the rows (rs_scrub_mfma_kernel and the records'
+// combine) or, for shapes without that kernel, from launch_verify and launch_crc in turn.
+// Stream-ordered, no synchronisation unless the stream's record scratch grows.
+int launch_scrub(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
+                 const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks,
+                 uint32_t* bad, uint32_t* raw, hipStream_t stream);
 // One tile's rs_verify_kernel fn over nblocks blocks, or (rplan given) its rs_locate_kernel or
 // rs_heal_kernel: one tile per wave unless waves_per_cu caps the grid, in launches whose tile
 // count fits 32 bits.  words: the last kernel argument, one 32-bit word per block: the candidates
@@ -314,7 +325,7 @@ int launch_stripe_tiles(rsmi_ctx* c, void* fn, const DevTile& t, const uint8_t* 
                         uint64_t data_bs, const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S,
                         uint64_t nblocks, uint32_t* bad, const RsPlanDev* rplan, void* words, hipStream_t stream);
 // The stream's entry of a per-stream scratch map (caller holds ctx->mu): verify_scratch, the
-// fallback's encoded rows; locate_scratch.  Past 32 streams the device is drained once and every
+// fallback's encoded rows; locate_scratch; scrub_scratch.  Past 32 streams the device is drained once and every
 // stream's scratch freed.
 rsmi_ctx::VerifyScratch& stream_scratch(std::map<hipStream_t, rsmi_ctx::VerifyScratch>& map, hipStream_t st);
 // The fallback of the shapes without a tile kernel: the encode of the data rows into the stream's

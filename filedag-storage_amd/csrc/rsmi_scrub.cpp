@@ -1,0 +1,165 @@
+// rsmi_scrub.cpp -- rsmi_scrub* (include/rsmi.h; see rsmi_impl.hpp for the file map): the first
+// pass of a scrub over stored stripes.  Both questions a scrub asks of every shard it reads, from
+// one read of the k + m rows: Encoder.Verify's flags (do the shards belong together?) and R(shard)
+// of the datanode entry checksum (is each shard the bytes that were stored?).
+// rs_scrub_mfma_kernel (rs_scrub_kernels.hip) writes the flags and the units' CRC records, and
+// rs_crc16_combine_mfma_kernel turns the records into R(row); shapes without a scrub kernel run
+// Verify and the CRC-16 rows pass one after the other.  The host paths are verify_host_impl's.
+
+#include "rsmi_impl.hpp"
+
+using namespace rsmi;
+using namespace rsmi::impl;
+
+namespace rsmi {
+namespace impl {
+
+int launch_scrub(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
+                 const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks,
+                 uint32_t* bad, uint32_t* raw, hipStream_t stream) {
+    if (nblocks == 0 || S == 0) return RSMI_OK;
+    const uint64_t k = uint64_t(c->k), m = uint64_t(c->m), n = k + m;
+    int rc;
+    const StripeLayout layout = stripe_layout(data, data_rs, data_bs, parity, parity_rs, parity_bs, S);
+    const bool aligned = layout == StripeLayout::kAligned, ua = layout == StripeLayout::kUA;
+    void* fn = nullptr;
+    if (plan.tiles.size() == 1 && plan.tiles[0].K <= 16 && (aligned || ua))
+        fn = (aligned ? scrub_kernels().fn : scrub_kernels().ua)[plan.tiles[0].K][plan.tiles[0].MT];
+    if (!fn) {
+        // m > 4, a K without an rs_scrub_mfma_kernel, unaligned rows shorter than 16 bytes: the two
+        // passes on this stream.  The correctness path of rare shapes.
+        if ((rc = launch_verify(c, plan, data, data_rs, data_bs, parity, parity_rs, parity_bs, S, nblocks, bad, stream)))
+            return rc;
+        HIP_TRY(hipMemsetAsync(raw, 0, nblocks * n * sizeof(uint32_t), stream));
+        if ((rc = launch_crc(c, data, data_rs, data_bs, uint32_t(k), S, nblocks, raw, n, stream, false))) return rc;
+        return launch_crc(c, parity, parity_rs, parity_bs, uint32_t(m), S, nblocks, raw + k, n, stream, false);
+    }
+    if ((rc = ensure_crc_tables(c))) return rc;
+    const DevTile& tile = plan.tiles[0];
+    const uint64_t cpb = (S + 15) / 16, tpb = (cpb + kWave - 1) / kWave;
+    const uint64_t upb = (tpb + kFusedUnitTiles - 1) / kFusedUnitTiles;
+    const uint64_t nacc = (n + 1) / 2;  // two-shard accumulators: a record byte per lane each
+    const uint64_t rec_per_block = upb * nacc * kWave;
+    // the units' records, per stream (the host pipeline runs on three)
+    rsmi_ctx::VerifyScratch& sc = stream_scratch(c->scrub_scratch, stream);
+    if ((rc = reserve_on(sc.p, sc.cap, nblocks * rec_per_block, stream))) return rc;
+    HIP_TRY(hipMemsetAsync(bad, 0, nblocks * m * sizeof(uint32_t), stream));
+    // A^e moves a row's value from the end of its last unit to the row's end
+    const int64_t unit_bytes = int64_t(kFusedUnitTiles) * kWave * 16;
+    const uint64_t e = uint64_t(((int64_t(S) - int64_t(upb) * unit_bytes) % int64_t(kCrcOrder) + kCrcOrder) % kCrcOrder);
+    Crc16Shift sh;
+    for (int b = 0; b < 16; b++) sh.col[b] = crc16_tables().shift(uint16_t(1u << b), e);
+    const RsPlanDev* pd = tile.dev;
+    uint32_t S32 = uint32_t(S), cpb32 = uint32_t(cpb), tpb32 = uint32_t(tpb), upb32 = uint32_t(upb), m32 = uint32_t(m);
+    const uint32_t* ctb = c->d_crc_tbl;
+    // launches of at most 2^31 units (32-bit unit index)
+    const uint64_t max_blocks = std::max<uint64_t>(1, (uint64_t(1) << 31) / upb);
+    for (uint64_t b0 = 0; b0 < nblocks; b0 += max_blocks) {
+        const uint64_t nb = std::min(max_blocks, nblocks - b0);
+        uint32_t nunits = uint32_t(nb * upb);
+        const uint8_t* inb = data + b0 * data_bs;
+        const uint8_t* parb = parity + b0 * parity_bs;
+        uint32_t* badb = bad + b0 * m;
+        uint8_t* rb = sc.p + b0 * rec_per_block;
+        void* args[] = {&pd,    &inb,   &parb,  &data_bs, &data_rs, &parity_bs, &parity_rs, &S32,
+                        &cpb32, &tpb32, &upb32, &nunits,  &badb,    &m32,       &ctb,       &rb};
+        HIP_TRY(hipLaunchKernel(fn, dim3(nunits), dim3(kWG), args, 0, stream));  // a workgroup per unit
+    }
+    // the records' combine, as behind rs_fused_mfma_kernel (launch_plan_crc): a persistent grid of
+    // up to 8 workgroups per CU, 4 waves each, over (block, 4-row group) items
+    uint32_t nacc32 = uint32_t(nacc), nsh32 = uint32_t(n);
+    uint64_t nb64 = nblocks;
+    const uint8_t* crec = sc.p;
+    void* cargs[] = {&ctb, &crec, &upb32, &nacc32, &nsh32, &sh, &nb64, &raw};
+    const uint64_t items = nblocks * ((n + 3) / 4);
+    const uint32_t grid = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>((items + 3) / 4, uint64_t(c->num_cu) * 8)));
+    HIP_TRY(hipLaunchKernel(crc16_combine_mfma_kernel(), dim3(grid), dim3(kWG), cargs, 0, stream));
+    char buf[96];
+    std::snprintf(buf, sizeof buf, "rs_scrub_mfma_kernel<K=%d,MT=%d>%s", tile.K, tile.MT, ua ? ",UA" : "");
+    set_last_kernel(c, buf);
+    return hip_status(hipGetLastError());
+}
+
+namespace {
+
+// Host-memory scrub on verify_host_impl's paths: the flags and, beside them in ctx->d_vbad, the raws.
+int scrub_host(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
+               size_t parity_block_stride, size_t S, size_t nblocks, uint32_t* bad_out, uint32_t* raw_out) {
+    if (int rc = check_stripe_host_args(c, data, data_block_stride, parity, parity_block_stride, S,
+                                        bad_out && raw_out ? bad_out : nullptr))
+        return rc;
+    if (nblocks == 0) return RSMI_OK;
+    const size_t m = size_t(c->m), n = size_t(c->k) + m;
+    const size_t flag_bytes = nblocks * m * sizeof(uint32_t), raw_bytes = nblocks * n * sizeof(uint32_t);
+    uint32_t* d_bad = nullptr;
+    uint32_t* d_raw = nullptr;
+    StripeCheck chk;
+    chk.prepare = [&]() -> int {
+        int rc = reserve(c->d_vbad, c->vbad_cap, flag_bytes + raw_bytes);
+        d_bad = reinterpret_cast<uint32_t*>(c->d_vbad);
+        d_raw = d_bad + nblocks * m;
+        return rc;
+    };
+    chk.launch = [&](const Plan& plan, const uint8_t* d, uint64_t d_rs, uint64_t d_bs, const uint8_t* p, uint64_t p_rs,
+                     uint64_t p_bs, uint64_t nb, uint64_t b0, hipStream_t st) -> int {
+        return launch_scrub(c, plan, d, d_rs, d_bs, p, p_rs, p_bs, S, nb, d_bad + b0 * m, d_raw + b0 * n, st);
+    };
+    chk.fetch = [&](hipStream_t st) -> int {
+        if (st) {
+            HIP_TRY(hipMemcpyAsync(bad_out, d_bad, flag_bytes, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(raw_out, d_raw, raw_bytes, hipMemcpyDeviceToHost, st));
+        } else {
+            HIP_TRY(hipMemcpy(bad_out, d_bad, flag_bytes, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(raw_out, d_raw, raw_bytes, hipMemcpyDeviceToHost));
+        }
+        return RSMI_OK;
+    };
+    return verify_host_impl(c, data, data_block_stride, parity, parity_block_stride, S, nblocks, chk);
+}
+
+}  // namespace
+
+}  // namespace impl
+}  // namespace rsmi
+
+extern "C" {
+
+int rsmi_scrub_batch_dev(rsmi_ctx* c, const uint8_t* d_data, size_t data_shard_stride, size_t data_block_stride,
+                         const uint8_t* d_parity, size_t parity_shard_stride, size_t parity_block_stride, size_t S,
+                         size_t nblocks, uint32_t* d_bad_out, uint32_t* d_raw_out, void* stream) try {
+    int rc = check_stripe_dev_args(c, d_data, data_shard_stride, d_parity, parity_shard_stride, S,
+                                   d_bad_out && d_raw_out ? d_bad_out : nullptr);
+    if (rc) return rc;
+    if (nblocks == 0) return RSMI_OK;
+    std::shared_ptr<Plan> plan;
+    std::unique_lock<std::mutex> lock;
+    if ((rc = begin_stripe_dev_call(c, lock, plan))) return rc;
+    return launch_scrub(c, *plan, d_data, data_shard_stride, data_block_stride, d_parity, parity_shard_stride,
+                        parity_block_stride, S, nblocks, d_bad_out, d_raw_out, static_cast<hipStream_t>(stream));
+} catch (...) {
+    return rsmi::impl::exception_status();
+}
+
+int rsmi_scrub_batch_host(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
+                          size_t parity_block_stride, size_t S, size_t nblocks, uint32_t* bad_out,
+                          uint32_t* raw16_out) try {
+    return scrub_host(c, data, data_block_stride, parity, parity_block_stride, S, nblocks, bad_out, raw16_out);
+} catch (...) {
+    return rsmi::impl::exception_status();
+}
+
+int rsmi_scrub(rsmi_ctx* c, const uint8_t* shards, size_t S, int* ok_out, uint32_t* raw_out) try {
+    if (!c || !shards || !ok_out || !raw_out) return RSMI_ERR_INVALID_ARG;
+    if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
+    const size_t k = size_t(c->k), m = size_t(c->m);
+    std::vector<uint32_t> bad(m, 0), raw(k + m, 0);
+    int rc = scrub_host(c, shards, k * S, shards + k * S, m * S, S, 1, bad.data(), raw.data());
+    if (rc) return rc;
+    *ok_out = std::all_of(bad.begin(), bad.end(), [](uint32_t x) { return x == 0; }) ? 1 : 0;
+    std::copy(raw.begin(), raw.end(), raw_out);
+    return RSMI_OK;
+} catch (...) {
+    return rsmi::impl::exception_status();
+}
+
+}  // extern "C"

@@ -98,6 +98,11 @@ def lib() -> ctypes.CDLL:
         "rsmi_verify_batch_host": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, u8p, c_size, c_size, c_size,
                                                   ctypes.c_void_p]),
         "rsmi_verify": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, ctypes.POINTER(ctypes.c_int)]),
+        "rsmi_scrub_batch_dev": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, u8p, c_size, c_size, c_size, c_size,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+        "rsmi_scrub_batch_host": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, u8p, c_size, c_size, c_size,
+                                                 ctypes.c_void_p, ctypes.c_void_p]),
+        "rsmi_scrub": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]),
         "rsmi_locate_batch_dev": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, u8p, c_size, c_size, c_size, c_size,
                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
         "rsmi_locate_batch_host": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, u8p, c_size, c_size, c_size,
@@ -317,6 +322,22 @@ class Codec:
         of block b differs from the encode of the block's data rows."""
         _check(lib().rsmi_verify_batch_host(self._h, data_ptr, data_bs, parity_ptr, parity_bs, S, nblocks, bad_ptr))
 
+    def scrub(self, shards, S: int) -> Tuple[bool, List[int]]:
+        """rsmi_scrub of one block of n*S contiguous bytes: (verify's answer, R(shard) of each of
+        the n shards as stored), from one read of the rows."""
+        src = shards if isinstance(shards, bytearray) else bytearray(shards)
+        ok = ctypes.c_int(-1)
+        raw = (ctypes.c_uint32 * self.n)()
+        _check(lib().rsmi_scrub(self._h, ctypes.addressof(_buf(src)) if src else None, S, ctypes.byref(ok), raw))
+        return ok.value == 1, list(raw)
+
+    def scrub_batch_host_ptr(self, data_ptr: int, data_bs: int, parity_ptr: int, parity_bs: int, S: int,
+                             nblocks: int, bad_ptr: int, raw_ptr: int) -> None:
+        """rsmi_scrub_batch_host: rsmi_verify_batch_host's flags in bad_ptr[b*m + j] and R(row) in
+        raw_ptr[b*n + r] (uint32, host memory, data rows first)."""
+        _check(lib().rsmi_scrub_batch_host(self._h, data_ptr, data_bs, parity_ptr, parity_bs, S, nblocks,
+                                           bad_ptr or None, raw_ptr or None))
+
     def locate(self, shards, S: int) -> int:
         """rsmi_locate of one block of n*S contiguous bytes: LocateClean, the index of the one
         shard that explains the damage, or LocateUnknown."""
@@ -483,6 +504,14 @@ class Codec:
         non-zero iff stored parity row j of block b is not the encode of the block's data rows."""
         _check(lib().rsmi_verify_batch_dev(self._h, d_data, data_rs, data_bs, d_parity, parity_rs, parity_bs, S,
                                            nblocks, d_bad, stream or None))
+
+    def scrub_batch_dev(self, d_data: int, data_rs: int, data_bs: int, d_parity: int, parity_rs: int,
+                        parity_bs: int, S: int, nblocks: int, d_bad: int, d_raw: int, stream: int = 0) -> None:
+        """rsmi_scrub_batch_dev: rsmi_verify_batch_dev's flags in d_bad[b*m + j] and what
+        rsmi_crc16_rows_dev writes for every row in d_raw[b*n + r] (uint32, device memory, data rows
+        first), from one read of the rows.  Stream-ordered."""
+        _check(lib().rsmi_scrub_batch_dev(self._h, d_data, data_rs, data_bs, d_parity, parity_rs, parity_bs, S,
+                                          nblocks, d_bad or None, d_raw or None, stream or None))
 
     def locate_batch_dev(self, d_data: int, data_rs: int, data_bs: int, d_parity: int, parity_rs: int,
                          parity_bs: int, S: int, nblocks: int, d_culprit: int, d_bad: int = 0, stream: int = 0) -> None:
@@ -821,6 +850,17 @@ class Erasure:
         rc, S = check_shards([len(s) if s else 0 for s in shards], nil_ok=False)
         _check(rc)
         return self.encoder().verify(bytearray(b"".join(shards)), S)
+
+    def scrub(self, shards: List[bytes]) -> Tuple[bool, List[int]]:
+        """The first pass of a scrub (rsmi_scrub): (verify's answer, R(shard) of every shard as
+        stored, ready for crc16_entry), from one read of the shards.  The shard list is checked as
+        verify checks it."""
+        n = self.data_blocks + self.parity_blocks
+        if len(shards) != n:
+            raise RsmiError(ErrTooFewShards)
+        rc, S = check_shards([len(s) if s else 0 for s in shards], nil_ok=False)
+        _check(rc)
+        return self.encoder().scrub(bytearray(b"".join(shards)), S)
 
     def locate(self, shards: List[bytes]) -> int:
         """Which shard breaks the stripe (rsmi_locate): LocateClean, the index of the one shard

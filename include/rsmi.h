@@ -41,8 +41,9 @@ extern "C" {
  * rsmi_heal_batch_dev), the mixed-batch reconstruct (rsmi_reconstruct_mixed_batch_dev,
  * rsmi_reconstruct_mixed_batch_host, rsmi_reconstruct_mixed_classify), the pair locate
  * (rsmi_locate_pair, rsmi_locate_pair_batch_host, rsmi_locate_pair_batch_dev,
- * rsmi_locate_pair_checks) and the pair heal (rsmi_heal_pair, rsmi_heal_pair_batch_host,
- * rsmi_heal_pair_batch_dev, rsmi_heal_pair_matrix). */
+ * rsmi_locate_pair_checks), the pair heal (rsmi_heal_pair, rsmi_heal_pair_batch_host,
+ * rsmi_heal_pair_batch_dev, rsmi_heal_pair_matrix) and the scrub (rsmi_scrub, rsmi_scrub_batch_host,
+ * rsmi_scrub_batch_dev). */
 #define RSMI_ABI_VERSION 5
 
 typedef struct rsmi_ctx rsmi_ctx;
@@ -252,6 +253,37 @@ int rsmi_verify_batch_host(rsmi_ctx* ctx, const uint8_t* data, size_t data_block
 
 /* Encoder.Verify of one block: n*S contiguous bytes; *ok_out = 1 iff every parity row matches. */
 int rsmi_verify(rsmi_ctx* ctx, const uint8_t* shards, size_t S, int* ok_out);
+
+/* ------------------------------------------------------------------ scrub: Verify and every shard's CRC-16 */
+
+/* A scrub of stored stripes asks two questions of every shard it reads: is it the bytes that were
+ * stored (the datanode's CRC-16 of the entry, server.go:70), and do the k+m shards belong together
+ * (Verify)?  These calls answer both from one read of the k+m rows: Verify's flags, and R(shard)
+ * of every data and parity row as stored, damaged or not, which rsmi_crc16_entry finishes on the
+ * host (see "datanode CRC-16" below).  The read-side twin of rsmi_encode_batch_dev_crc.  Shapes
+ * without a one-pass kernel (m > 4, a k without one, unaligned rows shorter than 16 bytes) run
+ * Verify and the CRC-16 rows pass one after the other, with the same results.  Nothing but the two
+ * outputs is written; bytes outside a row (padding) reach neither.  None of these calls takes or
+ * clears the per-thread wait hook. */
+
+/* Device-resident: layout, argument checks and fast-path alignment as rsmi_verify_batch_dev.
+ * d_bad_out[b*m + j] (nblocks*m words) is exactly rsmi_verify_batch_dev's flags, and
+ * d_raw_out[b*(k+m) + r] (nblocks*(k+m) words, data rows first) exactly what rsmi_crc16_rows_dev
+ * writes for that row: R(shard) over bytes [0, S).  Both are required, both device memory.
+ * Stream-ordered, no sync (the stream's scratch grows behind one wait for that stream). */
+int rsmi_scrub_batch_dev(rsmi_ctx* ctx, const uint8_t* d_data, size_t data_shard_stride, size_t data_block_stride,
+                         const uint8_t* d_parity, size_t parity_shard_stride, size_t parity_block_stride,
+                         size_t S, size_t nblocks, uint32_t* d_bad_out, uint32_t* d_raw_out, void* stream);
+
+/* Host memory, layout and the three paths of rsmi_verify_batch_host (page-locked rows are read in
+ * place, once); bad_out[b*m + j] and raw16_out[b*(k+m) + r] in host memory, both required. */
+int rsmi_scrub_batch_host(rsmi_ctx* ctx, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
+                          size_t parity_block_stride, size_t S, size_t nblocks, uint32_t* bad_out,
+                          uint32_t* raw16_out);
+
+/* One block of n*S contiguous bytes: *ok_out = 1 iff every parity row matches, raw_out[0..k+m) =
+ * R(shard). */
+int rsmi_scrub(rsmi_ctx* ctx, const uint8_t* shards, size_t S, int* ok_out, uint32_t* raw_out);
 
 /* ------------------------------------------------------------------ locate: which shard is wrong */
 
