@@ -351,4 +351,91 @@ void* crc16_rows_kernel(bool aligned) {
                    : reinterpret_cast<void*>(&rs_crc16_rows_kernel);
 }
 
+// The named forms of the rows passes (NamedRows, rs_crc_rows.hpp): R(row) of the rows a device array
+// names, per block, in a stripe's two halves.  Tables, folds, scans and end shifts are the regular
+// passes'; only the item source differs.  UA (either half off the 16-byte grid): the memory-grid
+// fold (RowSpan), an item's end mis bytes before its end on the row's grid, for both folds.
+
+// the nibble fold: rows_pipe_named with the tile-set tables G, A^8192 from P4 and crc_item_out
+template <bool UA>
+__global__ __launch_bounds__(kWG) void rs_crc16_named_kernel(const uint32_t* __restrict__ tbl, NamedRowsArgs a,
+                                                             uint64_t S, uint32_t tpb, uint32_t nsup, uint64_t nitems,
+                                                             uint32_t* __restrict__ out, Crc16Shift sh) {
+    __shared__ uint32_t s_tbl[kCrcP4Words + kCrcGWords];
+    const CrcNibTables T = crc_stage_nib(s_tbl, tbl);
+    const uint32_t col_e = lane_column(sh.col);  // A^E, lane-distributed
+    const uint64_t last_end = crc_last_end(tpb);
+    const RowsWave wv = rows_wave<kWG>();
+    const uint32_t lane = wv.lane;
+    const NamedRows src{a, tpb, nsup, out};
+    rows_pipe_named<UA>(
+        wv, src, S, nitems, [&](uint32_t i, const u32x4& v) { return crc_nib_chunk(T.nb + 1024 * i, v); },
+        [&](uint32_t acc) { return crc_pow4(T.sQ, 13, acc); },
+        [&](uint32_t acc, const NamedRows::Item& x, uint32_t mis) {
+            crc_item_out(T.sQ, lane, acc, crc_item_end(RowsItem{x.b, x.r, x.t0, x.nt}) - mis, last_end, col_e,
+                         src.word(x));
+        });
+}
+
+// the fold on the matrix cores: rs_crc16_rows_mfma_kernel's item, for the items that name a row
+template <bool UA>
+__global__ __launch_bounds__(kWG) void rs_crc16_named_mfma_kernel(const uint32_t* __restrict__ tbl, NamedRowsArgs a,
+                                                                  uint64_t S, uint32_t tpb, uint32_t nsup,
+                                                                  uint64_t nitems, uint32_t* __restrict__ out,
+                                                                  Crc16Shift sh) {
+    __shared__ uint32_t s_p4[kCrcP4Words];
+    __shared__ u32x4 s_w[kCrcMWWords / 4];
+    for (int i = threadIdx.x; i < kCrcP4Words; i += kWG) s_p4[i] = tbl[kCrcP4Off + i];
+    for (int i = threadIdx.x; i < kCrcMWWords / 4; i += kWG)
+        s_w[i] = reinterpret_cast<const u32x4*>(tbl + kCrcMWOff)[i];
+    __syncthreads();
+    const uint16_t* sQ = reinterpret_cast<const uint16_t*>(s_p4);
+    const uint32_t col_e = lane_column(sh.col);  // A^E, lane-distributed
+    const uint64_t last_end = crc_last_end(tpb);
+    const RowsWave wv = rows_wave<kWG>();
+    const uint32_t lane = wv.lane, m = lane & 15u;
+    const NamedRows src{a, tpb, nsup, out};
+    for (uint64_t it = wv.it0; it < nitems; it += wv.nw) {
+        NamedRows::Item x;
+        if (!src.item(it, x)) continue;  // the entry names nothing
+        const RowSpan<UA> sp = row_span<UA>(src.row(x), S);
+        uint32_t acc = 0;  // lanes 0..15: class m's running value
+        for (uint32_t g0 = 0; g0 < x.nt; g0 += kCrcSegTiles) {
+            const uint32_t t0 = x.t0 + g0;
+            const uint32_t nt = x.nt - g0 < uint32_t(kCrcSegTiles) ? x.nt - g0 : uint32_t(kCrcSegTiles);
+            u32x4 v[kCrcSegTiles];
+#pragma unroll
+            for (int i = 0; i < kCrcSegTiles; i++) v[i] = sp.load(t0 + i, lane);
+            mfma_v4f c = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int i = 0; i < kCrcSegTiles; i++) {
+                if (uint32_t(i) < nt) {
+                    u32x4 d = v[i];
+                    mask_row_ends<UA>(d, t0 + i, lane, sp);
+#pragma unroll
+                    for (int q = 0; q < 4; q++) {
+                        const mfma_v8i bd = fp4_bit_plane(d, q);
+                        const u32x4 wt = s_w[(i * 4 + q) * kWave + lane];
+                        const mfma_v8i aw = {int(wt[0]), int(wt[1]), int(wt[2]), int(wt[3]), 0, 0, 0, 0};
+                        c = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(aw, bd, c, 4, 4, 0, 127, 0, 127);
+                    }
+                }
+            }
+            acc = crc_pow4(sQ, 13, acc) ^ ballot_class_value(c, m);  // earlier groups move 8 KiB further
+        }
+        const uint32_t val = uint32_t(__builtin_amdgcn_readlane(int(crc_class_scan(sQ, acc, m)), 15));
+        crc_item_add(sQ, lane, val,
+                     uint32_t((last_end - crc_item_end(RowsItem{x.b, x.r, x.t0, x.nt}) + sp.mis) % kCrcOrder), col_e,
+                     src.word(x));
+    }
+}
+
+void* crc16_named_kernel(bool mfma, bool aligned) {
+    if (mfma)
+        return aligned ? reinterpret_cast<void*>(&rs_crc16_named_mfma_kernel<false>)
+                       : reinterpret_cast<void*>(&rs_crc16_named_mfma_kernel<true>);
+    return aligned ? reinterpret_cast<void*>(&rs_crc16_named_kernel<false>)
+                   : reinterpret_cast<void*>(&rs_crc16_named_kernel<true>);
+}
+
 }  // namespace rsmi

@@ -240,6 +240,116 @@ __global__ __launch_bounds__(kCrc32MfmaWG) void rs_crc32_rows_mfma_kernel(
     }
 }
 
+// The named forms (NamedRows, rs_crc_rows.hpp): R32(row) of the rows a device array names, per
+// block, in a stripe's two halves; tables, folds, scans and end shifts as above.
+
+// the nibble fold: rows_pipe_named with rs_crc32_rows_pipe_kernel's lambdas
+template <bool UA>
+__global__ __launch_bounds__(kWG) void rs_crc32_named_kernel(const uint32_t* __restrict__ tbl, NamedRowsArgs a,
+                                                             uint64_t S, uint32_t tpb, uint32_t nsup, uint64_t nitems,
+                                                             uint32_t* __restrict__ out, Crc32Shift sh) {
+    __shared__ uint32_t s_tbl[kCrc32LdsWords];
+    for (int i = threadIdx.x; i < kCrc32LdsWords; i += kWG) s_tbl[i] = tbl[i];
+    __syncthreads();
+    const uint8_t* nb = reinterpret_cast<const uint8_t*>(s_tbl);
+    const uint32_t* sS = s_tbl + kCrc32FoldWords;
+    const uint32_t* sG = sS + kCrc32ScanPowers * kCrc32PowWords;
+    const uint32_t* sC = tbl + kCrc32LdsWords;
+    const uint32_t q8 = uint32_t(S / (kCrc32SegTiles * 1024));
+    const uint32_t l32 = threadIdx.x & 31;
+    const uint32_t col_r = lane_column(sh.col);  // A^r8, lane-distributed
+    const RowsWave wv = rows_wave<kWG>();
+    const uint32_t lane = wv.lane;
+    const NamedRows src{a, tpb, nsup, out};
+    rows_pipe_named<UA>(
+        wv, src, S, nitems, [&](uint32_t i, const u32x4& v) { return crc32_nib_chunk(nb + 2048 * i, v); },
+        [&](uint32_t acc) { return pow_nib(sG, acc); },
+        [&](uint32_t acc, const NamedRows::Item& x, uint32_t mis) {
+            crc32_item_out(sS, sC, col_r, lane, l32, acc, (x.t0 + x.nt - 1) / kCrc32SegTiles, q8, mis, src.word(x));
+        });
+}
+
+// the fold on the matrix cores: rs_crc32_rows_mfma_kernel's item, for the items that name a row
+template <bool UA>
+__global__ __launch_bounds__(kCrc32MfmaWG) void rs_crc32_named_mfma_kernel(const uint32_t* __restrict__ tbl,
+                                                                           NamedRowsArgs a, uint64_t S, uint32_t tpb,
+                                                                           uint32_t nsup, uint64_t nitems,
+                                                                           uint32_t* __restrict__ out, Crc32Shift sh) {
+    constexpr int kWWords = kCrc32MWWords * kCrc32MfmaTiles / kCrc32SegTiles;  // the staged tiles' weights
+    __shared__ u32x4 s_w[kWWords / 4];
+    __shared__ uint32_t s_pw[6 * kCrc32PowWords];  // SN[0..3] | SG | SG4
+    {
+        const u32x4* w = reinterpret_cast<const u32x4*>(tbl + kCrc32MWOff + (kCrc32MWWords - kWWords));
+        for (int i = threadIdx.x; i < kWWords / 4; i += kCrc32MfmaWG) s_w[i] = w[i];
+        for (int i = threadIdx.x; i < 4 * kCrc32PowWords; i += kCrc32MfmaWG) s_pw[i] = tbl[kCrc32FoldWords + i];
+        for (int i = threadIdx.x; i < kCrc32PowWords; i += kCrc32MfmaWG) {
+            s_pw[4 * kCrc32PowWords + i] = tbl[kCrc32FoldWords + 6 * kCrc32PowWords + i];
+            s_pw[5 * kCrc32PowWords + i] = tbl[kCrc32SG4Off + i];
+        }
+    }
+    __syncthreads();
+    const uint32_t* sS = s_pw;
+    const uint32_t* sG = s_pw + 4 * kCrc32PowWords;
+    const uint32_t* sG4 = s_pw + 5 * kCrc32PowWords;
+    const uint32_t* sC = tbl + kCrc32LdsWords;
+    const uint32_t q8 = uint32_t(S / (kCrc32SegTiles * 1024));
+    const uint32_t l32 = threadIdx.x & 31;
+    const uint32_t col_r = lane_column(sh.col);  // A^r8, lane-distributed
+    const RowsWave wv = rows_wave<kCrc32MfmaWG>();
+    const uint32_t lane = wv.lane, m = lane & 15u;
+    const NamedRows src{a, tpb, nsup, out};
+    for (uint64_t it = wv.it0; it < nitems; it += wv.nw) {
+        NamedRows::Item x;
+        if (!src.item(it, x)) continue;  // the entry names nothing
+        const RowSpan<UA> sp = row_span<UA>(src.row(x), S);
+        uint32_t acc = 0;  // lanes 0..15: class m's running value
+        for (uint32_t g0 = 0; g0 < x.nt; g0 += kCrc32SegTiles) {
+            const uint32_t t0 = x.t0 + g0;
+            const uint32_t nt = x.nt - g0 < uint32_t(kCrc32SegTiles) ? x.nt - g0 : uint32_t(kCrc32SegTiles);
+            u32x4 v[kCrc32SegTiles];
+#pragma unroll
+            for (int i = 0; i < kCrc32SegTiles; i++) v[i] = sp.load(t0 + i, lane);
+            uint32_t gval = 0;  // the group's value, relative to its end
+#pragma unroll
+            for (int hh = 0; hh < kCrc32SegTiles / kCrc32MfmaTiles; hh++) {
+                mfma_v4f c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int i = hh * kCrc32MfmaTiles; i < (hh + 1) * kCrc32MfmaTiles; i++) {
+                    if (uint32_t(i) < nt) {
+                        u32x4 d = v[i];
+                        mask_row_ends<UA>(d, t0 + i, lane, sp);
+#pragma unroll
+                        for (int q = 0; q < 4; q++) {
+                            const mfma_v8i bd = fp4_bit_plane(d, q);
+                            const int ti = i % kCrc32MfmaTiles;
+                            const u32x4 w0 = s_w[((ti * 4 + q) * 2 + 0) * kWave + lane];
+                            const u32x4 w1 = s_w[((ti * 4 + q) * 2 + 1) * kWave + lane];
+                            const mfma_v8i a0 = {int(w0[0]), int(w0[1]), int(w0[2]), int(w0[3]), 0, 0, 0, 0};
+                            const mfma_v8i a1 = {int(w1[0]), int(w1[1]), int(w1[2]), int(w1[3]), 0, 0, 0, 0};
+                            c0 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a0, bd, c0, 4, 4, 0, 127, 0, 127);
+                            c1 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a1, bd, c1, 4, 4, 0, 127, 0, 127);
+                        }
+                    }
+                }
+                const uint32_t val = ballot_class_value(c0, m) | (ballot_class_value(c1, m) << 16);
+                gval = (hh == 0 ? 0u : pow_nib(sG4, gval)) ^ val;  // an earlier half moves 4 KiB further
+            }
+            acc = (g0 == 0 ? 0u : pow_nib(sG, acc)) ^ gval;  // earlier groups move 8 KiB further from the end
+        }
+        acc = rows_scan<4>(acc, m, [&](int j, uint32_t s) { return pow_nib(sS + j * kCrc32PowWords, s); });
+        const uint32_t val = uint32_t(__builtin_amdgcn_readlane(int(acc), 15));  // wave-uniform from here
+        crc32_shift_out(sC, col_r, lane, l32, val, (x.t0 + x.nt - 1) / kCrc32SegTiles, q8, sp.mis, src.word(x));
+    }
+}
+
+void* crc32_named_kernel(bool mfma, bool aligned) {
+    if (mfma)
+        return aligned ? reinterpret_cast<void*>(&rs_crc32_named_mfma_kernel<false>)
+                       : reinterpret_cast<void*>(&rs_crc32_named_mfma_kernel<true>);
+    return aligned ? reinterpret_cast<void*>(&rs_crc32_named_kernel<false>)
+                   : reinterpret_cast<void*>(&rs_crc32_named_kernel<true>);
+}
+
 void* crc32_rows_mfma_kernel(bool aligned) {
     return aligned ? reinterpret_cast<void*>(&rs_crc32_rows_mfma_kernel<false>)
                    : reinterpret_cast<void*>(&rs_crc32_rows_mfma_kernel<true>);

@@ -2,7 +2,8 @@
 // rs_crc32_kernels.hip): the work items of a launch, a row's span on the memory's 16-byte grid, the
 // software-pipelined nibble pass, the matrix-core passes' operand and read-out, and the scans.  The
 // CRC-specific parts (the nibble fold, the power lookups, the end shift, the staged tables) come in
-// as lambdas; DESIGN.md §4.2.
+// as lambdas; DESIGN.md §4.2.  The named forms of the passes (NamedRows, rows_pipe_named: the rows a
+// device array names) share everything but the item loop.
 //
 // A launch's work item is a super-segment of one row: up to kRowsSupGroups groups of kRowsSegTiles
 // consecutive 1 KiB tiles, a lane folding its 16-byte chunk of every tile.  A group's tiles fold
@@ -50,6 +51,51 @@ __device__ __forceinline__ RowsItem rows_item(uint64_t it, uint32_t nsup, uint32
     x.nt = tpb - x.t0 < kSup ? tpb - x.t0 : kSup;
     return x;
 }
+
+// The named item source (rsmi_crc_named_rows_dev): the rows a device array names.  Item `it` is
+// super-segment it % nsup of entry it / nsup, entry e block e / slots, slot e % slots.  The entry
+// word is device data the host never saw: it is loaded once per item (wave-uniform, a scalar load)
+// and range-checked before anything is formed from it, so an entry outside [0, n) costs that load
+// and nothing else -- no address, no row load, no table lookup, no output access.  Row r < k lies in
+// the data half, row k + j in the parity half; the output word is the entry's (out_n == 0:
+// out[b*slots + s]) or the row's (out[b*out_n + r], what the mixed reconstruct returns).
+struct NamedRows {
+    struct Item {
+        uint64_t b, e;
+        uint32_t r, t0, nt;  // block, entry, row in block, first tile, tiles in the item
+    };
+    NamedRowsArgs a;
+    uint32_t tpb, nsup;
+    uint32_t* out;
+    // item `it` (< the launch's items) -> x; false where its entry names no row
+    __device__ __forceinline__ bool item(uint64_t it, Item& x) const {
+        constexpr uint32_t kSup = kRowsSupGroups * kRowsSegTiles;
+        uint32_t sup;
+        if (it < (uint64_t(1) << 32)) {  // 32-bit divisions (scalar), the common case
+            const uint32_t i32 = uint32_t(it), e = i32 / nsup;
+            sup = i32 - e * nsup;
+            x.e = e;
+            x.b = e / a.slots;
+        } else {
+            sup = uint32_t(it % nsup);
+            x.e = it / nsup;
+            x.b = x.e / a.slots;
+        }
+        x.r = uint32_t(__builtin_amdgcn_readfirstlane(a.rows[x.e]));
+        if (x.r >= a.n) return false;  // unsigned: the negative verdicts and anything past the last row
+        x.t0 = sup * kSup;
+        x.nt = tpb - x.t0 < kSup ? tpb - x.t0 : kSup;
+        return true;
+    }
+    __device__ __forceinline__ const uint8_t* row(const Item& x) const {
+        const bool d = x.r < a.k;
+        return (d ? a.data : a.parity) + x.b * (d ? a.data_bs : a.parity_bs) +
+               uint64_t(d ? x.r : x.r - a.k) * (d ? a.data_rs : a.parity_rs);
+    }
+    __device__ __forceinline__ uint32_t* word(const Item& x) const {
+        return a.out_n ? out + x.b * a.out_n + x.r : out + x.e;
+    }
+};
 
 // The persistent grid: a wave takes items it0, it0 + nw, ... (WG threads per workgroup).
 struct RowsWave {
@@ -180,6 +226,82 @@ __device__ __forceinline__ void rows_pipe(const RowsWave& wv, const uint8_t* __r
     };
     if (wv.it0 >= nitems) return;
     Unit cur = at(wv.it0);
+    u32x4 va[kU], vb[kU];
+    issue(cur, va);
+    for (;;) {
+        Unit nx = next(cur);
+        bool more = nx.it < nitems;
+        issue(more ? nx : cur, vb);
+        finish(cur, va);
+        if (!more) break;
+        cur = nx;
+        nx = next(cur);
+        more = nx.it < nitems;
+        issue(more ? nx : cur, va);
+        finish(cur, vb);
+        if (!more) break;
+        cur = nx;
+    }
+}
+
+// rows_pipe over the named item source.  The regular passes keep rows_pipe as it is: routing them
+// through a source object changes their register allocation (tools/isa_diff.py), so
+// the named kernels have this loop of their own.  It differs in where a unit comes from: at() walks
+// to the wave's next item whose entry names a row, or to the end, before anything is issued for it,
+// so the prefetch only ever touches a named row (past the wave's last named unit it re-reads that
+// unit), and a wave none of whose items names a row issues no row load at all.
+//   item_out(acc, x, mis) the lanes' values of item x -> src.word(x)
+template <bool UA, class Fold, class StepGroup, class ItemOut>
+__device__ __forceinline__ void rows_pipe_named(const RowsWave& wv, const NamedRows& src, uint64_t S, uint64_t nitems,
+                                                Fold&& fold, StepGroup&& step_group, ItemOut&& item_out) {
+    constexpr int kU = kRowsSegTiles / 2;  // tiles per unit
+    const uint32_t lane = wv.lane;
+    struct Unit {
+        uint64_t it;  // >= nitems: the end, x unset
+        NamedRows::Item x;
+        uint32_t h;
+    };
+    auto at = [&](uint64_t it) -> Unit {
+        Unit u;
+        u.h = 0;
+        while (it < nitems && !src.item(it, u.x)) it += wv.nw;
+        u.it = it;
+        return u;
+    };
+    auto next = [&](const Unit& u) -> Unit {
+        if ((u.h + 1) * kU < u.x.nt) return Unit{u.it, u.x, u.h + 1};
+        return at(u.it + wv.nw);
+    };
+    auto issue = [&](const Unit& u, u32x4(&v)[kU]) {
+        const RowSpan<UA> sp = row_span<UA>(src.row(u.x), S);
+#pragma unroll
+        for (int i = 0; i < kU; i++) v[i] = sp.load(u.x.t0 + u.h * kU + i, lane);
+    };
+    uint32_t acc = 0, gs = 0;
+    auto finish = [&](const Unit& u, u32x4(&v)[kU]) {
+        const NamedRows::Item& x = u.x;
+        const uint32_t u0 = u.h * kU, t0 = x.t0 + u0;
+        const uint32_t nt = x.nt - u0 < uint32_t(kU) ? x.nt - u0 : uint32_t(kU);
+        const RowSpan<UA> sp = row_span<UA>(src.row(x), S);
+#pragma unroll
+        for (int i = 0; i < kU; i++) {
+            if (uint32_t(i) < nt) {
+                mask_row_ends<UA>(v[i], t0 + i, lane, sp);
+                gs ^= fold(kU * (u.h & 1) + i, v[i]);
+            }
+        }
+        const bool item_end = u0 + kU >= x.nt;
+        if ((u.h & 1) || item_end) {
+            acc = step_group(acc) ^ gs;
+            gs = 0;
+        }
+        if (item_end) {
+            item_out(acc, x, sp.mis);
+            acc = 0;
+        }
+    };
+    Unit cur = at(wv.it0);
+    if (cur.it >= nitems) return;
     u32x4 va[kU], vb[kU];
     issue(cur, va);
     for (;;) {

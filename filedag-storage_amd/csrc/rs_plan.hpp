@@ -327,5 +327,19 @@ void* crc16_combine_kernel(int ns2);  // ns2 = record dwords per lane (rows / 8,
 void* crc16_combine_mfma_kernel();    // records of rs_fused_mfma_kernel
 void* crc32_rows_kernel(bool aligned);
 void* crc32_rows_mfma_kernel(bool aligned);  // the fold on the matrix cores (512-thread workgroups)
+// The named rows passes (rs_crc_rows.hpp NamedRows): the rows of a stripe's two halves that a
+// device array names.  rows[b*slots + s] in [0, n) names row r of block b (r < k at data + b*data_bs
+// + r*data_rs, else parity + b*parity_bs + (r-k)*parity_rs); out_n == 0: the entry's checksum goes
+// to out[b*slots + s], otherwise to out[b*out_n + r].
+struct NamedRowsArgs {
+    const int32_t* rows;
+    const uint8_t* data;
+    uint64_t data_bs, data_rs;
+    const uint8_t* parity;
+    uint64_t parity_bs, parity_rs;
+    uint32_t k, n, slots, out_n;
+};
+void* crc16_named_kernel(bool mfma, bool aligned);
+void* crc32_named_kernel(bool mfma, bool aligned);  // mfma: 512-thread workgroups
 
 }  // namespace rsmi

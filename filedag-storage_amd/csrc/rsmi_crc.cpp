@@ -1,7 +1,8 @@
 // rsmi_crc.cpp -- the datanode entry checksum (dag/node/datanode/server.go:58-75) on the GPU:
 // the R(row) pass, the encode with the CRC fused in, and the host-side header fold
 // (crc16.hpp has the algebra; rsmi_impl.hpp the file map); and the mutcask value checksum
-// (CRC-32 IEEE, kv/mutcask/cask.go:73-97; crc32.hpp) as an R(row) pass.
+// (CRC-32 IEEE, kv/mutcask/cask.go:73-97; crc32.hpp) as an R(row) pass; and both over the rows a
+// device array names (rsmi_crc_named_rows_dev).
 #include "rsmi_impl.hpp"
 
 using namespace rsmi;
@@ -154,6 +155,63 @@ int launch_rebuilt_crcs(rsmi_ctx* c, const uint8_t* base, uint64_t rpitch, uint6
         if (d32 && (rc = launch_crc32(c, row, rpitch, bstride, 1, S, nblocks, d32 + r, n, stream))) return rc;
     }
     return RSMI_OK;
+}
+
+// R(row) and/or R32(row) of the rows a.rows names (rs_plan.hpp NamedRowsArgs; nblocks * a.slots
+// entries in device memory, read on the stream), XORed into d16 / d32 (either may be null) at the
+// entry's or the row's word; zero: the nblocks * (a.out_n ? a.out_n : a.slots) words of each are
+// zeroed on the stream first.  One launch per checksum; grid caps and end shifts are launch_crc's
+// and launch_crc32's.  Stream-ordered.
+int launch_crc_named(rsmi_ctx* c, const NamedRowsArgs& a, uint64_t S, uint64_t nblocks, uint32_t* d16, uint32_t* d32,
+                     hipStream_t stream, bool zero) {
+    if (!nblocks || !a.slots || (!d16 && !d32)) return RSMI_OK;
+    const uint64_t seg = uint64_t(kWave) * 16 * kCrc32SegTiles;
+    if (d32 && S / seg >= (uint64_t(1) << kCrc32SegPowers)) return RSMI_ERR_INVALID_ARG;  // rows below 4 GiB
+    int rc;
+    if (d16 && (rc = ensure_crc_tables(c))) return rc;
+    if (d32 && (rc = ensure_crc32_tables(c))) return rc;
+    const uint64_t words = nblocks * (a.out_n ? a.out_n : a.slots);
+    if (zero && d16) HIP_TRY(hipMemsetAsync(d16, 0, words * 4, stream));
+    if (zero && d32) HIP_TRY(hipMemsetAsync(d32, 0, words * 4, stream));
+    if (S == 0) return RSMI_OK;  // R(empty) = 0
+    // the aligned kernels only when every row of both halves starts on the memory's 16-byte grid;
+    // otherwise rows fold on that grid, where a row spans its misalignment (< 16) + S bytes
+    const bool aligned = rows_aligned(a.data, a.data_rs, a.data_bs) && rows_aligned(a.parity, a.parity_rs, a.parity_bs);
+    const uint64_t span = S + (aligned ? 0 : 15);
+    NamedRowsArgs na = a;
+    uint64_t S64 = S;
+    if (d16) {
+        const bool mfma = c->opt_crc16_fold == 1;
+        RowsGrid g = rows_grid(c, span, a.slots, nblocks, kWG / kWave, 96);
+        // A^E, E = S - (end of the last item, counted in whole 8-tile groups), mod 32767
+        const uint64_t last_end = (uint64_t(g.tpb) + kCrcSegTiles - 1) / kCrcSegTiles * kCrcSegTiles * kWave * 16;
+        const int64_t E = ((int64_t(S) - int64_t(last_end)) % int64_t(kCrcOrder) + kCrcOrder) % kCrcOrder;
+        Crc16Shift sh;
+        for (int b = 0; b < 16; b++) sh.col[b] = crc16_tables().shift(uint16_t(1u << b), uint64_t(E));
+        const uint32_t* tb = c->d_crc_tbl;
+        void* args[] = {&tb, &na, &S64, &g.tpb, &g.nsup, &g.nitems, &d16, &sh};
+        HIP_TRY(hipLaunchKernel(crc16_named_kernel(mfma, aligned), dim3(g.wgs), dim3(kWG), args, 0, stream));
+        set_last_kernel(c, std::string(mfma ? "rs_crc16_named_mfma_kernel" : "rs_crc16_named_kernel") +
+                               (aligned ? "" : ",UA"));
+    }
+    if (d32) {
+        const bool mfma = c->opt_crc32_fold == 1;
+        // the matrix-core form keeps its 8-wave workgroups and 48 waves per CU
+        const uint64_t wpg = mfma ? uint64_t(kCrc32MfmaWG) / kWave : kWG / kWave;
+        RowsGrid g = rows_grid(c, span, a.slots, nblocks, wpg, mfma && !kCrc32MfmaHalf ? 48 : 96);
+        if (c->crc32_shift_S != S) {  // the per-launch shift to the row's end, cached for the last S
+            crc32_tables().shift_columns(S % seg, c->crc32_shift.col);
+            c->crc32_shift_S = S;
+        }
+        Crc32Shift sh = c->crc32_shift;
+        const uint32_t* tb = c->d_crc32_tbl;
+        void* args[] = {&tb, &na, &S64, &g.tpb, &g.nsup, &g.nitems, &d32, &sh};
+        HIP_TRY(hipLaunchKernel(crc32_named_kernel(mfma, aligned), dim3(g.wgs), dim3(uint32_t(wpg * kWave)), args, 0,
+                                stream));
+        set_last_kernel(c, std::string(mfma ? "rs_crc32_named_mfma_kernel" : "rs_crc32_named_kernel") +
+                               (aligned ? "" : ",UA"));
+    }
+    return hip_status(hipGetLastError());
 }
 
 // Any single-tile plan with the CRC-16 fused in (rs_fast_kernel CRC variants), then R(row) of
@@ -387,6 +445,30 @@ int rsmi_crc32_rows_dev(rsmi_ctx* c, const uint8_t* d_rows, size_t shard_stride,
                                          out_block_stride, st),
                             label};
     });
+}
+
+int rsmi_crc_named_rows_dev(rsmi_ctx* c, const uint8_t* d_data, size_t data_shard_stride, size_t data_block_stride,
+                            const uint8_t* d_parity, size_t parity_shard_stride, size_t parity_block_stride, size_t S,
+                            size_t nblocks, const int32_t* d_rows, int slots, uint32_t* d_raw16_out,
+                            uint32_t* d_raw32_out, void* stream) try {
+    // rsmi_verify_batch_dev's checks first (its output: whichever of the two is given)
+    const void* out = d_raw16_out ? static_cast<const void*>(d_raw16_out) : static_cast<const void*>(d_raw32_out);
+    int rc = check_stripe_dev_args(c, d_data, data_shard_stride, d_parity, parity_shard_stride, S,
+                                   out ? out : static_cast<const void*>(c));
+    if (rc) return rc;
+    if (!d_rows || slots < 1 || slots > c->n || !out) return RSMI_ERR_INVALID_ARG;
+    if (d_raw32_out && S / (uint64_t(kWave) * 16 * kCrc32SegTiles) >= (uint64_t(1) << kCrc32SegPowers))
+        return RSMI_ERR_INVALID_ARG;  // rows below 4 GiB, as rsmi_crc32_rows_dev
+    if (nblocks == 0) return RSMI_OK;
+    std::lock_guard<std::mutex> g(c->mu);
+    if ((rc = ensure_device(c))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const NamedRowsArgs a{d_rows,   d_data,  data_block_stride,   data_shard_stride,
+                          d_parity, parity_block_stride, parity_shard_stride,
+                          uint32_t(c->k), uint32_t(c->n), uint32_t(slots), 0};  // out_n 0: by slot
+    return launch_crc_named(c, a, S, nblocks, d_raw16_out, d_raw32_out, static_cast<hipStream_t>(stream), true);
+} catch (...) {
+    return rsmi::impl::exception_status();
 }
 
 int rsmi_crc_rows_host(rsmi_ctx* c, const uint8_t* rows, size_t row_stride, size_t nrows, size_t S,

@@ -1,7 +1,8 @@
 // rsmi_impl.hpp -- internals shared by the C-ABI implementation files (include/rsmi.h):
 //   rsmi_core.cpp      contexts, coding plans, kernel dispatch, options, device-resident calls
 //   rsmi_host.cpp      host-memory calls: zero-copy single kernel, copy-engine pipeline
-//   rsmi_crc.cpp       datanode CRC-16 on the GPU (separate pass and fused into the encode)
+//   rsmi_crc.cpp       datanode CRC-16 on the GPU (separate pass and fused into the encode); the rows
+//                      passes over named rows (rsmi_crc_named_rows_dev)
 //   rsmi_coalesce.cpp  group commit of concurrent single-block calls
 //   rsmi_verify.cpp    Encoder.Verify: stored parity checked against the data rows; what the three
 //                      stripe checks share: the layout test, the tile launch, the scratch-encode
@@ -417,8 +418,11 @@ void classify_mixed(const rsmi_ctx* c, size_t nblocks, const uint8_t* present, c
 // The launches of blocks [b0, b0 + nb) of a classed batch (caller holds ctx->mu, the device is
 // bound): rs_mixed_kernel per class, launch_plan per run of fallback blocks.  base: block b0's
 // first row.  Stream-ordered, no synchronisation unless the stream's scratch grows or wraps.
+// d16 / d32 (device memory, either may be null): block b0's n words of the by-row checksums, zeroed
+// by the caller on the stream; R / R32 of every row the launches rebuild is added there by the named
+// rows pass behind them, its rows array riding in the same upload as the classes' lists.
 int launch_mixed(rsmi_ctx* c, const MixedBatch& mb, uint8_t* base, uint64_t rs, uint64_t bs, uint64_t S, uint64_t b0,
-                 uint64_t nb, hipStream_t stream);
+                 uint64_t nb, hipStream_t stream, uint32_t* d16 = nullptr, uint32_t* d32 = nullptr);
 int ensure_crc_tables(rsmi_ctx* c);
 int ensure_crc32_tables(rsmi_ctx* c);
 // R(row) / R32(row) of the rows the plan rebuilt (want && !present), one row per block at
@@ -429,6 +433,10 @@ int launch_rebuilt_crcs(rsmi_ctx* c, const uint8_t* base, uint64_t rpitch, uint6
                         hipStream_t stream);
 int launch_crc32(rsmi_ctx* c, const uint8_t* base, uint64_t rpitch, uint64_t bstride, uint32_t nrows, uint64_t S,
                  uint64_t nblocks, uint32_t* out, uint64_t out_bs, hipStream_t stream);
+// R(row) / R32(row) of the rows a device array names (rs_plan.hpp NamedRowsArgs) into d16 / d32
+// (either may be null), by slot or by row; zero: the outputs are zeroed on the stream first
+int launch_crc_named(rsmi_ctx* c, const NamedRowsArgs& a, uint64_t S, uint64_t nblocks, uint32_t* d16, uint32_t* d32,
+                     hipStream_t stream, bool zero);
 int launch_crc(rsmi_ctx* c, const uint8_t* base, uint64_t rpitch, uint64_t bstride, uint32_t nrows, uint64_t S,
                uint64_t nblocks, uint32_t* out, uint64_t out_bs, hipStream_t stream, bool zero = true);
 int launch_encode_crc(rsmi_ctx* c, const Plan& plan, const uint8_t* in, size_t in_rs, size_t in_bs, uint8_t* out,

@@ -6,7 +6,8 @@
 // class over that class's tiles; a wave finds its block and plan through the class's list.
 // Blocks whose plan has more than one tile, whose K has no rs_mixed_kernel, or whose layout is
 // neither aligned nor unaligned-window take the uniform call's launch_plan, one per run of
-// consecutive blocks with equal masks: the correctness path of rare shapes.
+// consecutive blocks with equal masks: the correctness path of rare shapes.  The _crcs forms add the
+// named rows pass (rsmi_crc.cpp launch_crc_named) over the rows just rebuilt, behind those launches.
 
 #include "rsmi_impl.hpp"
 
@@ -110,8 +111,9 @@ int mixed_words(rsmi_ctx* c, hipStream_t st, size_t need, uint8_t*& h, uint8_t*&
 }  // namespace
 
 int launch_mixed(rsmi_ctx* c, const MixedBatch& mb, uint8_t* base, uint64_t rs, uint64_t bs, uint64_t S, uint64_t b0,
-                 uint64_t nb, hipStream_t stream) {
+                 uint64_t nb, hipStream_t stream, uint32_t* d16, uint32_t* d32) {
     if (nb == 0 || S == 0) return RSMI_OK;
+    const bool crcs = d16 || d32;
     const size_t n = size_t(c->n), npat = mb.keys.size();
     // launch_plan's layout test, the rows being read and written in place
     const StripeLayout layout = stripe_layout(base, rs, bs, base, rs, bs, S);
@@ -161,11 +163,20 @@ int launch_mixed(rsmi_ctx* c, const MixedBatch& mb, uint8_t* base, uint64_t rs, 
                 nfast++;
             }
         }
-        if (nfast) {
+        // with checksums: the rows every block of the segment rebuilds, as the named rows pass reads
+        // them (slots = the most rows a block rebuilds, unused slots -1), behind the lists
+        uint32_t slots = 0;
+        if (crcs)
+            for (uint64_t b = 0; b < sn; b++)
+                if (cls[mb.pat[s0 + b]] != kNoLaunch) slots = std::max<uint32_t>(slots, mb.key_rows[mb.pat[s0 + b]]);
+        const size_t rows_bytes = size_t(sn) * slots * sizeof(int32_t);
+        const int32_t* d_rows = nullptr;
+        if (nfast || slots) {
             // one upload: the patterns' plan pointers, then the classes' lists in ascending MT
             const size_t ptr_bytes = round_up(npat * sizeof(const RsPlanDev*), 16);
+            const size_t list_bytes = round_up(nfast * sizeof(MixedEntry), 16);
             uint8_t *h = nullptr, *d = nullptr;
-            int rc = mixed_words(c, stream, ptr_bytes + nfast * sizeof(MixedEntry), h, d);
+            int rc = mixed_words(c, stream, ptr_bytes + list_bytes + rows_bytes, h, d);
             if (rc) return rc;
             auto* hp = reinterpret_cast<const RsPlanDev**>(h);
             for (size_t p = 0; p < npat; p++) hp[p] = cls[p] > 0 ? plans[p]->tiles[0].dev : nullptr;
@@ -175,6 +186,20 @@ int launch_mixed(rsmi_ctx* c, const MixedBatch& mb, uint8_t* base, uint64_t rs, 
                 list_off[mt] = off;
                 if (!list[mt].empty()) std::memcpy(h + off, list[mt].data(), list[mt].size() * sizeof(MixedEntry));
                 off += list[mt].size() * sizeof(MixedEntry);
+            }
+            if (slots) {
+                off = ptr_bytes + list_bytes;
+                int32_t* hr = reinterpret_cast<int32_t*>(h + off);
+                for (uint64_t b = 0; b < sn; b++) {
+                    const uint32_t p = mb.pat[s0 + b];
+                    uint32_t s = 0;
+                    if (cls[p] != kNoLaunch)
+                        for (size_t i = 0; i < n; i++)
+                            if (mb.keys[p][i] == '2') hr[b * slots + s++] = int32_t(i);
+                    while (s < slots) hr[b * slots + s++] = -1;
+                }
+                d_rows = reinterpret_cast<const int32_t*>(d + off);
+                off += rows_bytes;
             }
             HIP_TRY(hipMemcpyAsync(d, h, off, hipMemcpyHostToDevice, stream));
             for (int mt = 1; mt <= kMaxMT; mt++) {
@@ -205,6 +230,14 @@ int launch_mixed(rsmi_ctx* c, const MixedBatch& mb, uint8_t* base, uint64_t rs, 
             }
             b = e;
         }
+        // the checksums of the rows just written, whatever rebuilt them: by row, behind the launches above
+        if (slots) {
+            const NamedRowsArgs a{d_rows, sbase, bs, rs, sbase + uint64_t(K) * rs, bs, rs,
+                                  uint32_t(K), uint32_t(n), slots, uint32_t(n)};
+            int rc = launch_crc_named(c, a, S, sn, d16 ? d16 + (s0 - b0) * n : nullptr,
+                                      d32 ? d32 + (s0 - b0) * n : nullptr, stream, false);
+            if (rc) return rc;
+        }
     }
     return hip_status(hipGetLastError());
 }
@@ -219,16 +252,23 @@ void write_status(const MixedBatch& mb, size_t nblocks, int32_t* status_out) {
 // The host-memory call on reconstruct_host_impl's three decisions: page-locked shards in place,
 // small pageable calls through the page-locked staging, everything else uploaded in ~64 MiB
 // chunks of whole blocks over the three staging slots.  Only wanted rows of blocks with status OK
-// are written into the caller's memory.
+// are written into the caller's memory.  crcs: raw16 / raw32[b*(k+m) + r] (host memory, not both
+// null) receive R / R32 of every row the call rebuilt and 0 elsewhere: the named rows pass runs where
+// the rows were rebuilt (in place, over the staging, over the chunk's device rows on its slot's
+// stream before the slot is reused), into ctx->d_crc / d_crc32, read back once at the end.
 int mixed_host_impl(rsmi_ctx* c, uint8_t* shards, size_t block_stride, size_t S, size_t nblocks,
-                    const uint8_t* present, const uint8_t* required, int data_only, int32_t* status_out) {
-    if (!c || !shards || !present) return RSMI_ERR_INVALID_ARG;
+                    const uint8_t* present, const uint8_t* required, int data_only, int32_t* status_out,
+                    bool crcs = false, uint32_t* raw16 = nullptr, uint32_t* raw32 = nullptr) {
+    if (!c || !shards || !present || (crcs && !raw16 && !raw32)) return RSMI_ERR_INVALID_ARG;
     if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
     if (block_stride < size_t(c->n) * S) return RSMI_ERR_INVALID_ARG;
     if (nblocks == 0) return RSMI_OK;
     MixedBatch mb;
     classify_mixed(c, nblocks, present, required, data_only, mb);
     if (mb.too_few && !status_out) return RSMI_ERR_TOO_FEW_SHARDS;
+    const size_t raw_sz = nblocks * size_t(c->n) * 4;
+    if (raw16) std::memset(raw16, 0, raw_sz);
+    if (raw32) std::memset(raw32, 0, raw_sz);
     if (!mb.work) {
         write_status(mb, nblocks, status_out);
         return RSMI_OK;
@@ -238,6 +278,10 @@ int mixed_host_impl(rsmi_ctx* c, uint8_t* shards, size_t block_stride, size_t S,
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = size_t(c->n), blk = n * S;
+    if (raw16 && (rc = reserve(c->d_crc, c->crc_cap, raw_sz))) return rc;
+    if (raw32 && (rc = reserve(c->d_crc32, c->crc32_cap, raw_sz))) return rc;
+    uint32_t* d16 = raw16 ? reinterpret_cast<uint32_t*>(c->d_crc) : nullptr;
+    uint32_t* d32 = raw32 ? reinterpret_cast<uint32_t*>(c->d_crc32) : nullptr;
     // the rows of block b the call moves: in, the present rows; out, the rows it rebuilt
     auto each_row = [&](size_t b, char which, auto&& fn) {
         const uint32_t p = mb.pat[b];
@@ -259,8 +303,14 @@ int mixed_host_impl(rsmi_ctx* c, uint8_t* shards, size_t block_stride, size_t S,
             dbs = blk;
             if (!dev) return RSMI_ERR_DEVICE;
         }
-        if ((rc = launch_mixed(c, mb, dev, S, dbs, S, 0, nblocks, st))) return rc;
+        if (d16) HIP_TRY(hipMemsetAsync(d16, 0, raw_sz, st));
+        if (d32) HIP_TRY(hipMemsetAsync(d32, 0, raw_sz, st));
+        if ((rc = launch_mixed(c, mb, dev, S, dbs, S, 0, nblocks, st, d16, d32))) return rc;
+        const uint32_t *h16, *h32;
+        if ((rc = readback(c, d16, d32, raw_sz, st, h16, h32))) return rc;
         HIP_TRY(hipStreamSynchronize(st));
+        if (raw16) std::memcpy(raw16, h16, raw_sz);
+        if (raw32) std::memcpy(raw32, h32, raw_sz);
         if (hs)
             for (size_t b = 0; b < nblocks; b++)
                 each_row(b, '2', [&](size_t i) { std::memcpy(shards + b * block_stride + i * S, hs + b * blk + i * S, S); });
@@ -283,7 +333,11 @@ int mixed_host_impl(rsmi_ctx* c, uint8_t* shards, size_t block_stride, size_t S,
         else
             for (size_t b = 0; b < nb; b++)
                 HIP_TRY(hipMemcpyAsync(st.d_lin + b * blk, h + b * block_stride, blk, hipMemcpyHostToDevice, st.stream));
-        if ((rc = launch_mixed(c, mb, st.d_lin, S, blk, S, b0, nb, st.stream))) return rc;
+        if (d16) HIP_TRY(hipMemsetAsync(d16 + b0 * n, 0, nb * n * 4, st.stream));
+        if (d32) HIP_TRY(hipMemsetAsync(d32 + b0 * n, 0, nb * n * 4, st.stream));
+        if ((rc = launch_mixed(c, mb, st.d_lin, S, blk, S, b0, nb, st.stream, d16 ? d16 + b0 * n : nullptr,
+                               d32 ? d32 + b0 * n : nullptr)))
+            return rc;
         for (size_t b = 0; b < nb; b++) {
             hipError_t e = hipSuccess;
             each_row(b0 + b, '2', [&](size_t r) {
@@ -295,6 +349,8 @@ int mixed_host_impl(rsmi_ctx* c, uint8_t* shards, size_t block_stride, size_t S,
         }
     }
     for (int s = 0; s < ns; s++) HIP_TRY(hipStreamSynchronize(c->staging[s].stream));
+    if (raw16) HIP_TRY(hipMemcpy(raw16, d16, raw_sz, hipMemcpyDeviceToHost));
+    if (raw32) HIP_TRY(hipMemcpy(raw32, d32, raw_sz, hipMemcpyDeviceToHost));
     write_status(mb, nblocks, status_out);
     return RSMI_OK;
 }
@@ -324,26 +380,62 @@ int rsmi_reconstruct_mixed_classify(const rsmi_ctx* c, size_t nblocks, const uin
     return rsmi::impl::exception_status();
 }
 
-int rsmi_reconstruct_mixed_batch_dev(rsmi_ctx* c, uint8_t* d_shards, size_t shard_stride, size_t block_stride, size_t S,
-                                     size_t nblocks, const uint8_t* present, const uint8_t* required, int data_only,
-                                     int32_t* status_out, void* stream) try {
-    if (!c || !d_shards || !present) return RSMI_ERR_INVALID_ARG;
+namespace {
+
+// rsmi_reconstruct_mixed_batch_dev, and with crcs its _crcs form: d16 / d32 (device memory, not
+// both null) are zeroed on the stream, so that form needs the device even with nothing to rebuild
+int mixed_dev_impl(rsmi_ctx* c, uint8_t* d_shards, size_t shard_stride, size_t block_stride, size_t S, size_t nblocks,
+                   const uint8_t* present, const uint8_t* required, int data_only, int32_t* status_out, bool crcs,
+                   uint32_t* d16, uint32_t* d32, void* stream) {
+    if (!c || !d_shards || !present || (crcs && !d16 && !d32)) return RSMI_ERR_INVALID_ARG;
     if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
     if (shard_stride < S) return RSMI_ERR_INVALID_ARG;
     if (nblocks == 0) return RSMI_OK;
     MixedBatch mb;
     classify_mixed(c, nblocks, present, required, data_only, mb);
     if (mb.too_few && !status_out) return RSMI_ERR_TOO_FEW_SHARDS;
-    if (mb.work) {
+    if (mb.work || crcs) {
         std::lock_guard<std::mutex> g(c->mu);
         int rc = ensure_device(c);
         if (rc) return rc;
         HIP_TRY(hipSetDevice(c->device));
-        rc = launch_mixed(c, mb, d_shards, shard_stride, block_stride, S, 0, nblocks, static_cast<hipStream_t>(stream));
-        if (rc) return rc;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        const size_t raw_sz = nblocks * size_t(c->n) * 4;
+        if (d16) HIP_TRY(hipMemsetAsync(d16, 0, raw_sz, st));
+        if (d32) HIP_TRY(hipMemsetAsync(d32, 0, raw_sz, st));
+        if (mb.work && (rc = launch_mixed(c, mb, d_shards, shard_stride, block_stride, S, 0, nblocks, st, d16, d32)))
+            return rc;
     }
     write_status(mb, nblocks, status_out);
     return RSMI_OK;
+}
+
+}  // namespace
+
+int rsmi_reconstruct_mixed_batch_dev(rsmi_ctx* c, uint8_t* d_shards, size_t shard_stride, size_t block_stride, size_t S,
+                                     size_t nblocks, const uint8_t* present, const uint8_t* required, int data_only,
+                                     int32_t* status_out, void* stream) try {
+    return mixed_dev_impl(c, d_shards, shard_stride, block_stride, S, nblocks, present, required, data_only, status_out,
+                          false, nullptr, nullptr, stream);
+} catch (...) {
+    return rsmi::impl::exception_status();
+}
+
+int rsmi_reconstruct_mixed_batch_dev_crcs(rsmi_ctx* c, uint8_t* d_shards, size_t shard_stride, size_t block_stride,
+                                          size_t S, size_t nblocks, const uint8_t* present, const uint8_t* required,
+                                          int data_only, int32_t* status_out, uint32_t* d_raw16_out,
+                                          uint32_t* d_raw32_out, void* stream) try {
+    return mixed_dev_impl(c, d_shards, shard_stride, block_stride, S, nblocks, present, required, data_only, status_out,
+                          true, d_raw16_out, d_raw32_out, stream);
+} catch (...) {
+    return rsmi::impl::exception_status();
+}
+
+int rsmi_reconstruct_mixed_batch_host_crcs(rsmi_ctx* c, uint8_t* shards, size_t block_stride, size_t S, size_t nblocks,
+                                           const uint8_t* present, const uint8_t* required, int data_only,
+                                           int32_t* status_out, uint32_t* raw16_out, uint32_t* raw32_out) try {
+    return mixed_host_impl(c, shards, block_stride, S, nblocks, present, required, data_only, status_out, true,
+                           raw16_out, raw32_out);
 } catch (...) {
     return rsmi::impl::exception_status();
 }

@@ -90,6 +90,15 @@ def lib() -> ctypes.CDLL:
                                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
         "rsmi_reconstruct_mixed_batch_host": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, c_size, u8p, u8p,
                                                              ctypes.c_int, ctypes.c_void_p]),
+        "rsmi_reconstruct_mixed_batch_dev_crcs": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, c_size, c_size, u8p,
+                                                                 u8p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                                 ctypes.c_void_p, ctypes.c_void_p]),
+        "rsmi_reconstruct_mixed_batch_host_crcs": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, c_size, u8p, u8p,
+                                                                  ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                                  ctypes.c_void_p]),
+        "rsmi_crc_named_rows_dev": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, u8p, c_size, c_size, c_size, c_size,
+                                                   ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p]),
         "rsmi_reconstruct_mixed_classify": (ctypes.c_int, [ctypes.c_void_p, c_size, u8p, u8p, ctypes.c_int,
                                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                            ctypes.POINTER(c_size)]),
@@ -598,6 +607,42 @@ class Codec:
         st = (ctypes.c_int32 * max(nblocks, 1))() if status else None
         _check(lib().rsmi_reconstruct_mixed_batch_host(self._h, ptr, bs, S, nblocks, p, q, 1 if data_only else 0, st))
         return list(st)[:nblocks] if status else None
+
+    def reconstruct_mixed_batch_dev_crcs(self, d_shards: int, rs: int, bs: int, S: int, nblocks: int, present,
+                                         required=None, data_only: bool = False, d_raw16: int = 0, d_raw32: int = 0,
+                                         stream: int = 0, status: bool = True) -> Optional[List[int]]:
+        """rsmi_reconstruct_mixed_batch_dev_crcs: reconstruct_mixed_batch_dev plus R / R32 of every
+        row it rebuilt in d_raw16 / d_raw32[b*(k+m) + r] (uint32, device memory, 0 elsewhere)."""
+        p, keep_p = self._masks(present, nblocks)
+        q, keep_q = self._masks(required, nblocks)
+        st = (ctypes.c_int32 * max(nblocks, 1))() if status else None
+        _check(lib().rsmi_reconstruct_mixed_batch_dev_crcs(self._h, d_shards, rs, bs, S, nblocks, p, q,
+                                                           1 if data_only else 0, st, d_raw16 or None,
+                                                           d_raw32 or None, stream or None))
+        return list(st)[:nblocks] if status else None
+
+    def reconstruct_mixed_batch_host_crcs_ptr(self, ptr: int, bs: int, S: int, nblocks: int, present, required=None,
+                                              data_only: bool = False, raw16_ptr: Optional[int] = None,
+                                              raw32_ptr: Optional[int] = None,
+                                              status: bool = True) -> Optional[List[int]]:
+        """rsmi_reconstruct_mixed_batch_host_crcs on nblocks blocks of host memory at ptr; the raw
+        checksums land in host memory at raw16_ptr / raw32_ptr (nblocks * (k+m) uint32 each)."""
+        p, keep_p = self._masks(present, nblocks)
+        q, keep_q = self._masks(required, nblocks)
+        st = (ctypes.c_int32 * max(nblocks, 1))() if status else None
+        _check(lib().rsmi_reconstruct_mixed_batch_host_crcs(self._h, ptr, bs, S, nblocks, p, q, 1 if data_only else 0,
+                                                            st, raw16_ptr or None, raw32_ptr or None))
+        return list(st)[:nblocks] if status else None
+
+    def crc_named_rows_dev(self, d_data: int, data_rs: int, data_bs: int, d_parity: int, parity_rs: int,
+                           parity_bs: int, S: int, nblocks: int, d_rows: int, slots: int, d_raw16: int = 0,
+                           d_raw32: int = 0, stream: int = 0) -> None:
+        """rsmi_crc_named_rows_dev: R / R32 of the rows d_rows[b*slots + s] names (int32, device memory;
+        heal_batch_dev's d_culprit with slots 1, heal_pair_batch_dev's d_pair with slots 2) in
+        d_raw16 / d_raw32[b*slots + s] (uint32, device memory), 0 where an entry names nothing."""
+        _check(lib().rsmi_crc_named_rows_dev(self._h, d_data, data_rs, data_bs, d_parity, parity_rs, parity_bs, S,
+                                             nblocks, d_rows or None, slots, d_raw16 or None, d_raw32 or None,
+                                             stream or None))
 
     def reconstruct_mixed_classify(self, nblocks: int, present, required=None, data_only: bool = False):
         """rsmi_reconstruct_mixed_classify, device-free: (statuses, rows written per block, the

@@ -42,8 +42,9 @@ extern "C" {
  * rsmi_reconstruct_mixed_batch_host, rsmi_reconstruct_mixed_classify), the pair locate
  * (rsmi_locate_pair, rsmi_locate_pair_batch_host, rsmi_locate_pair_batch_dev,
  * rsmi_locate_pair_checks), the pair heal (rsmi_heal_pair, rsmi_heal_pair_batch_host,
- * rsmi_heal_pair_batch_dev, rsmi_heal_pair_matrix) and the scrub (rsmi_scrub, rsmi_scrub_batch_host,
- * rsmi_scrub_batch_dev). */
+ * rsmi_heal_pair_batch_dev, rsmi_heal_pair_matrix), the scrub (rsmi_scrub, rsmi_scrub_batch_host,
+ * rsmi_scrub_batch_dev) and the checksums of named rows (rsmi_crc_named_rows_dev,
+ * rsmi_reconstruct_mixed_batch_dev_crcs, rsmi_reconstruct_mixed_batch_host_crcs). */
 #define RSMI_ABI_VERSION 5
 
 typedef struct rsmi_ctx rsmi_ctx;
@@ -217,6 +218,31 @@ int rsmi_reconstruct_mixed_batch_dev(rsmi_ctx* ctx, uint8_t* d_shards, size_t sh
 int rsmi_reconstruct_mixed_batch_host(rsmi_ctx* ctx, uint8_t* shards, size_t block_stride, size_t S, size_t nblocks,
                                       const uint8_t* present, const uint8_t* required, int data_only,
                                       int32_t* status_out);
+
+/* rsmi_reconstruct_mixed_batch_dev (same arguments, results, statuses and writes) plus the raw
+ * checksums of every row it rebuilt: d_raw16_out / d_raw32_out[b*(k+m) + r] = R / R32 of row r of
+ * block b where the call wrote that row, 0 everywhere else -- rows that are present, rows that are
+ * not wanted, blocks with RSMI_ERR_TOO_FEW_SHARDS -- as rsmi_reconstruct_rows_batch_host_crcs defines
+ * them (device memory, nblocks*(k+m) words each, either may be NULL, not both: RSMI_ERR_INVALID_ARG
+ * with the NULL checks).  The outputs are zeroed on the stream and the rows pass over the rebuilt
+ * rows (rsmi_crc_named_rows_dev's kernels) follows the rebuild on it; the rows it visits ride in
+ * the same upload as the blocks' classes, so no copy and no wait is added.  A batch with nothing to
+ * rebuild still zeroes the outputs on the stream: unlike the call above it then needs the device
+ * (RSMI_ERR_NO_DEVICE without one).  When the call fails as a whole the outputs are unspecified. */
+int rsmi_reconstruct_mixed_batch_dev_crcs(rsmi_ctx* ctx, uint8_t* d_shards, size_t shard_stride, size_t block_stride,
+                                          size_t S, size_t nblocks, const uint8_t* present, const uint8_t* required,
+                                          int data_only, int32_t* status_out, uint32_t* d_raw16_out,
+                                          uint32_t* d_raw32_out, void* stream);
+
+/* rsmi_reconstruct_mixed_batch_host plus the same checksums in host memory (raw16_out / raw32_out,
+ * nblocks*(k+m) words each, either may be NULL, not both), on each of its three paths from the GPU
+ * where the rows were rebuilt.  A batch with nothing to rebuild zeroes them and returns RSMI_OK
+ * without a device.  RepairDataNode's Puts of rows rebuilt from a mixed flush carry sender
+ * checksums as rsmi_reconstruct_rows_batch_host_crcs gives them for a uniform one. */
+int rsmi_reconstruct_mixed_batch_host_crcs(rsmi_ctx* ctx, uint8_t* shards, size_t block_stride, size_t S,
+                                           size_t nblocks, const uint8_t* present, const uint8_t* required,
+                                           int data_only, int32_t* status_out, uint32_t* raw16_out,
+                                           uint32_t* raw32_out);
 
 /* Host-only, works without a GPU, like rsmi_decode_matrix: what the two calls above will do with
  * these masks.  Every output may be NULL.  status_out[b]: as above.  rows_out[b]: the rows the call
@@ -641,6 +667,34 @@ int rsmi_reconstruct_batch_host_verify(rsmi_ctx* ctx, uint8_t* shards, size_t bl
 int rsmi_reconstruct_rows_batch_host_crcs(rsmi_ctx* ctx, uint8_t* shards, size_t block_stride, size_t S,
                                           size_t nblocks, const uint8_t* present, const uint8_t* required,
                                           uint32_t* raw16_out, uint32_t* raw32_out);
+
+/* ------------------------------------------------------------------ checksums of named rows */
+
+/* The calls that rewrite rows on the device (rsmi_heal_batch_dev, rsmi_heal_pair_batch_dev, the
+ * mixed reconstruct) write a different set of rows in every block.  The checksums of exactly those
+ * rows are the second witness of a heal (R(healed row) against the stored entry checksum shows a
+ * clean codeword that is not the original) and the sender checksums of a repaired shard's Put.
+ *
+ * R(row) and/or R32(row) of the rows a device array names, per block.  Layout and fast-path
+ * alignment as rsmi_verify_batch_dev (two halves: row r < k in the data half, row k + j in the
+ * parity half).  d_rows: DEVICE memory, nblocks * slots int32, read on the stream, so an array
+ * written by an earlier launch on that stream (rsmi_heal_batch_dev's d_culprit_out with slots 1,
+ * rsmi_heal_pair_batch_dev's d_pair_out with slots 2) is consumed with no host round trip.  An
+ * entry in [0, k+m) names that row of its block; every other value (RSMI_LOCATE_CLEAN,
+ * RSMI_LOCATE_UNKNOWN, anything out of range) names nothing, and no address is formed from it.
+ * d_raw16_out / d_raw32_out[b*slots + s] (device memory, either may be NULL, not both; zeroed on
+ * the stream first) = R / R32 over bytes [0, S) of the row entry (b, s) names, 0 where it names
+ * nothing; rsmi_crc16_entry / rsmi_crc32_entry finish them on the host.  Nothing else is written;
+ * only named rows are read (padding of a named row may be read, as everywhere).  The same row may
+ * be named twice.  Stream-ordered, no sync; the wait hook is neither taken nor cleared.
+ * Arguments: rsmi_verify_batch_dev's checks first, in its order and with its statuses; then
+ * d_rows == NULL, slots outside [1, k+m] or both outputs NULL -> RSMI_ERR_INVALID_ARG; a row of
+ * 4 GiB or more with d_raw32_out set -> RSMI_ERR_INVALID_ARG (as rsmi_crc32_rows_dev); nblocks == 0
+ * -> RSMI_OK; all before any device access. */
+int rsmi_crc_named_rows_dev(rsmi_ctx* ctx, const uint8_t* d_data, size_t data_shard_stride, size_t data_block_stride,
+                            const uint8_t* d_parity, size_t parity_shard_stride, size_t parity_block_stride, size_t S,
+                            size_t nblocks, const int32_t* d_rows, int slots, uint32_t* d_raw16_out,
+                            uint32_t* d_raw32_out, void* stream);
 
 /* ------------------------------------------------------------------ device groups (several GPUs, one process) */
 

@@ -7,7 +7,8 @@ For every object file both directories hold (or the named units), the device cod
 out of the host object's .hip_fatbin section (llvm-objcopy, clang-offload-bundler), disassembled (llvm-objdump -d) and split at the
 function symbols; addresses and encodings are dropped, so two functions are equal when they hold
 the same instructions with the same operands.  Prints one line per unit and the count compared;
-exits non-zero when a function differs or exists on one side only."""
+functions only the new build holds are counted as added, not as differing.  Exits non-zero when a
+function differs or only the old build holds it."""
 import os
 import re
 import subprocess
@@ -31,7 +32,7 @@ def functions(obj, tmp):
         if m:
             name = m.group(1)
             out[name] = []
-        elif name and line.strip():
+        elif name and line.strip() and line.strip() != "...":  # "...": the padding objdump elides after a function
             # drop the trailing address comment; branch targets stay symbolic (<name+0x..>)
             out[name].append(re.sub(r"\s*//.*$", "", line).strip())
     return out
@@ -40,19 +41,22 @@ def functions(obj, tmp):
 def main(old, new, units):
     if not units:
         units = sorted(f for f in os.listdir(old) if f.endswith(".o") and os.path.exists(os.path.join(new, f)))
-    total = bad = 0
+    total = bad = added = 0
     with tempfile.TemporaryDirectory() as tmp:
         for u in units:
             try:
                 a, b = functions(os.path.join(old, u), tmp), functions(os.path.join(new, u), tmp)
             except subprocess.CalledProcessError:
                 continue  # no device code in this object
-            diff = sorted(n for n in set(a) | set(b) if a.get(n) != b.get(n))
+            diff = sorted(n for n in a if a[n] != b.get(n))
+            more = len(set(b) - set(a))
             total += len(set(a) & set(b))
             bad += len(diff)
-            print("%-28s %4d functions, %d differ%s" % (u, len(set(a) & set(b)), len(diff),
-                                                        ": " + ", ".join(diff[:3]) if diff else ""))
-    print("%d compared, %d differ" % (total, bad))
+            added += more
+            print("%-28s %4d functions, %d differ%s%s" % (u, len(set(a) & set(b)), len(diff),
+                                                          ", %d added" % more if more else "",
+                                                          ": " + ", ".join(diff[:3]) if diff else ""))
+    print("%d compared, %d differ%s" % (total, bad, ", %d added" % added if added else ""))
     return 1 if bad or not total else 0
 
 
