@@ -171,52 +171,45 @@ const FastKernelTable& fast_kernels();
 void* generic_kernel();
 void* repitch_kernel();
 
-// Encoder.Verify (rs_verify_kernels.hip): rs_verify_kernel per (K, MT), aligned and
-// unaligned-window layouts (null when K has no instantiation), and the compare of the fallback
-// (encode into scratch, then rs_compare_rows_kernel)
-struct VerifyKernelTable {
+// The tile kernels of the calls over stored stripes, one table per call: a kernel per (K, MT), on
+// aligned and on unaligned-window layouts (null where the shape has none).  The calls' own names
+// for it follow.
+struct StripeKernelTable {
     void* fn[17][kMaxMT + 1];
     void* ua[17][kMaxMT + 1];
 };
+
+// Encoder.Verify (rs_verify_kernels.hip): rs_verify_kernel per (K, MT), aligned and
+// unaligned-window layouts (null when K has no instantiation), and the compare of the fallback
+// (encode into scratch, then rs_compare_rows_kernel)
+using VerifyKernelTable = StripeKernelTable;
 const VerifyKernelTable& verify_kernels();
 void* compare_rows_kernel();
 
 // rsmi_scrub (rs_scrub_kernels.hip): rs_scrub_mfma_kernel per (K, MT), the shapes of
 // rs_verify_kernel, aligned and unaligned-window layouts (null: Verify and the CRC-16 rows pass,
 // one after the other)
-struct ScrubKernelTable {
-    void* fn[17][kMaxMT + 1];
-    void* ua[17][kMaxMT + 1];
-};
+using ScrubKernelTable = StripeKernelTable;
 const ScrubKernelTable& scrub_kernels();
 
 // rsmi_locate (rs_locate_kernels.hip): rs_locate_kernel per (K, MT = m), m = 2..4, aligned and
 // unaligned-window layouts (null when the shape has none), the verdict kernel that follows every
 // locate launch, and the byte-granular kernel of the fallback
-struct LocateKernelTable {
-    void* fn[17][kMaxMT + 1];
-    void* ua[17][kMaxMT + 1];
-};
+using LocateKernelTable = StripeKernelTable;
 const LocateKernelTable& locate_kernels();
 void* locate_verdict_kernel();
 void* locate_rows_kernel();
 
 // rsmi_heal (rs_heal_kernels.hip): rs_heal_kernel per (K, MT = m), the shapes of rs_locate_kernel,
 // and the byte-granular kernel of the fallback
-struct HealKernelTable {
-    void* fn[17][kMaxMT + 1];
-    void* ua[17][kMaxMT + 1];
-};
+using HealKernelTable = StripeKernelTable;
 const HealKernelTable& heal_kernels();
 void* heal_rows_kernel();
 
 // rsmi_locate_pair (rs_pair_kernels.hip): rs_locate_pair_kernel per (K, MT = m), the K of
 // rs_locate_kernel with m = 3..4 (m <= 2 names no pair), aligned and unaligned-window layouts; the
 // verdict kernel that ends every pair call, and the byte-granular kernel of the fallback
-struct PairKernelTable {
-    void* fn[17][kMaxMT + 1];
-    void* ua[17][kMaxMT + 1];
-};
+using PairKernelTable = StripeKernelTable;
 const PairKernelTable& pair_kernels();
 void* pair_verdict_kernel();
 void* pair_rows_kernel();
@@ -234,10 +227,7 @@ constexpr int pair_words(int n) { return (n * (n - 1) / 2 + 31) / 32; }
 // has one column per explanation of a block: the C(n, 2) pairs {x, y} at pair_bit(n, x, y), then the n
 // single shards.  Column e carries D's four coefficients in its output slots (D[0][l0], D[0][l1],
 // D[1][l0], D[1][l1]) and l0 | l1 << 8 in in_row[e].
-struct HealPairKernelTable {
-    void* fn[17][kMaxMT + 1];
-    void* ua[17][kMaxMT + 1];
-};
+using HealPairKernelTable = StripeKernelTable;
 const HealPairKernelTable& heal_pair_kernels();
 void* heal_pair_rows_kernel();
 constexpr int heal_pair_entries(int n) { return n * (n - 1) / 2 + n; }

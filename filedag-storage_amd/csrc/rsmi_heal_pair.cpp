@@ -4,9 +4,10 @@
 // stream, rs_heal_pair_kernel (rs_heal_pair_kernels.hip), which reads the two verdict words of
 // every block and rewrites the rows they name; there is no host round trip in between.  Shapes
 // without an rs_locate_kernel encode the data rows into scratch once more, chunk by chunk, and
-// run the byte-granular rs_heal_pair_rows_kernel.  m = 2 names no pair: rs_heal_kernel runs on
-// rsmi_locate's verdicts (launch_heal_named, rsmi_heal.cpp).  The host paths are Verify's
-// (verify_host_impl) with a write-back leg of up to two rows per block.
+// run the byte-granular rs_heal_pair_rows_kernel (launch_heal_rows, rsmi_heal.cpp).  m = 2 names
+// no pair: rs_heal_kernel runs on rsmi_locate's verdicts (launch_heal_named, rsmi_heal.cpp).  The
+// host entries are verdicts_host_impl's (rsmi_verify.cpp) with the write-back leg, up to two rows
+// per block.
 
 #include "rsmi_impl.hpp"
 
@@ -97,133 +98,28 @@ int heal_pair_plan(rsmi_ctx* c, std::shared_ptr<Plan>& out) {
 // Pair heal of nblocks blocks (caller holds ctx->mu, the device is bound): launch_locate_pair's
 // outputs, then the heal launch, stream-ordered.  out is the caller's verdicts and the heal
 // kernel's input at once.
-int launch_heal_pair(rsmi_ctx* c, const Plan& plan, uint8_t* data, uint64_t data_rs, uint64_t data_bs, uint8_t* parity,
-                     uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks, int32_t* out, uint32_t* bad,
+int launch_heal_pair(rsmi_ctx* c, const Plan& plan, const StripeRows& rows, int32_t* out, uint32_t* bad,
                      hipStream_t stream) {
-    if (nblocks == 0 || S == 0) return RSMI_OK;
+    if (rows.nblocks == 0 || rows.S == 0) return RSMI_OK;
     PairLaunch pl;
-    int rc = launch_locate_pair(c, plan, data, data_rs, data_bs, parity, parity_rs, parity_bs, S, nblocks, out, bad,
-                                stream, &pl);
+    int rc = launch_locate_pair(c, plan, rows, out, bad, stream, &pl);
     if (rc) return rc;
     // m = 1: nothing is ever named.  m = 2: no pair is; rsmi_heal's launch on rsmi_locate's verdicts
     if (c->m == 1) return RSMI_OK;
-    if (c->m == 2)
-        return launch_heal_named(c, plan, pl.fused, data, data_rs, data_bs, parity, parity_rs, parity_bs, S, nblocks,
-                                 pl.culprit, stream);
+    if (c->m == 2) return launch_heal_named(c, plan, pl.fused, rows, pl.culprit, stream);
     if (pl.fused != StripeLayout::kNeither) {
         // the heal kernel of the layout rs_locate_kernel ran on
-        const bool aligned = pl.fused == StripeLayout::kAligned;
         const DevTile& t = plan.tiles[0];
-        void* fn = (aligned ? heal_pair_kernels().fn : heal_pair_kernels().ua)[t.K][t.MT];
+        void* fn = stripe_kernel(heal_pair_kernels(), pl.fused, t);
         if (!fn) return RSMI_ERR_DEVICE;  // a pair kernel without its heal kernel: a build error
         std::shared_ptr<Plan> hp;
         if ((rc = heal_pair_plan(c, hp))) return rc;
-        // launch_stripe_tiles' own split (a launch's tile count fits 32 bits), made here as
-        // launch_locate_pair makes it: the verdicts are two words per block
-        const uint64_t tpb = ((S + 15) / 16 + uint64_t(kWave) - 1) / uint64_t(kWave);
-        const uint64_t max_blocks = std::max<uint64_t>(1, (uint64_t(1) << 31) / tpb);
-        for (uint64_t b0 = 0; b0 < nblocks; b0 += max_blocks) {
-            const uint64_t nb = std::min(max_blocks, nblocks - b0);
-            rc = launch_stripe_tiles(c, fn, t, data + b0 * data_bs, data_rs, data_bs, parity + b0 * parity_bs, parity_rs,
-                                     parity_bs, S, nb, nullptr, hp->tiles[0].dev, out + 2 * b0, stream);
-            if (rc) return rc;
-        }
-        char buf[96];
-        std::snprintf(buf, sizeof buf, "rs_heal_pair_kernel<K=%d,MT=%d>%s", t.K, t.MT, aligned ? "" : ",UA");
-        set_last_kernel(c, buf);
-        return hip_status(hipGetLastError());
+        // rs_heal_kernel's arguments, the verdicts two words per block
+        if ((rc = launch_stripe_tiles(c, fn, t, rows, nullptr, 0, hp->tiles[0].dev, out, 2, stream))) return rc;
+        return tiles_launched(c, "heal_pair", pl.fused, t);
     }
-    // The fallback's scratch rows are gone (every 64 MiB chunk reuses them): the data rows are
-    // encoded again, chunk by chunk, and each chunk healed before the next one's encode, as
-    // rsmi_heal's fallback does.
-    if ((rc = ensure_locate_tables(c))) return rc;
-    rc = encode_into_scratch(
-        c, plan, data, data_rs, data_bs, S, nblocks, stream,
-        [&](uint64_t b0, uint64_t nb, const uint8_t* enc, uint64_t enc_rs, uint64_t enc_bs) -> int {
-            uint8_t* datab = data + b0 * data_bs;
-            uint8_t* parb = parity + b0 * parity_bs;
-            uint32_t k32 = uint32_t(c->k), m32 = uint32_t(c->m);
-            const int32_t* verdict = out + 2 * b0;
-            const uint8_t* tbl = c->d_locate_tbl;
-            const uint32_t gx = uint32_t(std::min<uint64_t>((S + kWG - 1) / kWG, 4096));
-            const uint32_t gy = uint32_t(std::min<uint64_t>(nb, 65535));
-            void* args[] = {&enc,  &enc_rs,    &enc_bs,    &datab, &data_rs, &data_bs, &parb, &parity_rs,
-                            &parity_bs, &S, &k32,   &m32,     &nb,      &verdict, &tbl};
-            HIP_TRY(hipLaunchKernel(heal_pair_rows_kernel(), dim3(gx, gy), dim3(kWG), args, 0, stream));
-            return RSMI_OK;
-        });
-    if (rc) return rc;
-    set_last_kernel(c, "rs_heal_pair_rows_kernel");
-    return hip_status(hipGetLastError());
-}
-
-// Host-memory pair heal on Verify's host paths: locate_pair_host_impl's buffers (the context's
-// device result buffer holds the flags, then two verdict words per block), and the write-back leg.
-int heal_pair_host_impl(rsmi_ctx* c, uint8_t* data, size_t data_block_stride, uint8_t* parity,
-                        size_t parity_block_stride, size_t S, size_t nblocks, int32_t* pair_out, uint32_t* bad_out) {
-    if (int rc = check_stripe_host_args(c, data, data_block_stride, parity, parity_block_stride, S, pair_out)) return rc;
-    if (nblocks == 0) return RSMI_OK;
-    const size_t k = size_t(c->k), m = size_t(c->m);
-    const size_t flag_bytes = nblocks * m * sizeof(uint32_t), verdict_bytes = 2 * nblocks * sizeof(int32_t);
-    // where the caller keeps row x of block b
-    auto home = [&](size_t b, size_t x) -> uint8_t* {
-        return x < k ? data + b * data_block_stride + x * S : parity + b * parity_block_stride + (x - k) * S;
-    };
-    uint32_t* d_bad = nullptr;
-    int32_t* d_pair = nullptr;
-    StripeCheck chk;
-    chk.prepare = [&]() -> int {
-        int rc = reserve(c->d_vbad, c->vbad_cap, flag_bytes + verdict_bytes);
-        d_bad = reinterpret_cast<uint32_t*>(c->d_vbad);
-        d_pair = reinterpret_cast<int32_t*>(d_bad + nblocks * m);
-        return rc;
-    };
-    chk.launch = [&](const Plan& plan, const uint8_t* d, uint64_t d_rs, uint64_t d_bs, const uint8_t* p, uint64_t p_rs,
-                     uint64_t p_bs, uint64_t nb, uint64_t b0, hipStream_t st) -> int {
-        // the rows are the caller's own (in place) or the call's staging: writable either way
-        return launch_heal_pair(c, plan, const_cast<uint8_t*>(d), d_rs, d_bs, const_cast<uint8_t*>(p), p_rs, p_bs, S,
-                                nb, d_pair + 2 * b0, d_bad + b0 * m, st);
-    };
-    chk.fetch = [&](hipStream_t st) -> int {
-        if (st) {
-            HIP_TRY(hipMemcpyAsync(pair_out, d_pair, verdict_bytes, hipMemcpyDeviceToHost, st));
-            if (bad_out) HIP_TRY(hipMemcpyAsync(bad_out, d_bad, flag_bytes, hipMemcpyDeviceToHost, st));
-        } else {
-            HIP_TRY(hipMemcpy(pair_out, d_pair, verdict_bytes, hipMemcpyDeviceToHost));
-            if (bad_out) HIP_TRY(hipMemcpy(bad_out, d_bad, flag_bytes, hipMemcpyDeviceToHost));
-        }
-        return RSMI_OK;
-    };
-    // the small staged call: the verdicts are in pair_out, the healed rows in the staging
-    chk.small_done = [&](const uint8_t* sd, const uint8_t* sp) -> int {
-        for (size_t b = 0; b < nblocks; b++)
-            for (int i = 0; i < 2; i++) {
-                const int32_t v = pair_out[2 * b + i];
-                if (v < 0) continue;
-                const size_t x = size_t(v);
-                if (x < k && sd) std::memcpy(home(b, x), sd + (b * k + x) * S, S);
-                if (x >= k && sp) std::memcpy(home(b, x), sp + (b * m + (x - k)) * S, S);
-            }
-        return RSMI_OK;
-    };
-    // the upload pipeline: a chunk's verdicts, then its healed rows from the device pitch to the
-    // caller's, before the staging slot is filled again
-    chk.chunk_done = [&](Staging& st, uint64_t b0, uint64_t nb, size_t Sp) -> int {
-        HIP_TRY(hipMemcpyAsync(pair_out + 2 * b0, d_pair + 2 * b0, 2 * nb * sizeof(int32_t), hipMemcpyDeviceToHost,
-                               st.stream));
-        HIP_TRY(hipStreamSynchronize(st.stream));
-        for (uint64_t b = 0; b < nb; b++)
-            for (int i = 0; i < 2; i++) {
-                const int32_t v = pair_out[2 * (b0 + b) + i];
-                if (v < 0) continue;
-                const size_t x = size_t(v);
-                const uint8_t* src = x < k ? st.d_in + (b * k + x) * Sp : st.d_out + (b * m + (x - k)) * Sp;
-                HIP_TRY(hipMemcpyAsync(home(b0 + b, x), src, S, hipMemcpyDeviceToHost, st.stream));
-            }
-        HIP_TRY(hipStreamSynchronize(st.stream));
-        return RSMI_OK;
-    };
-    return verify_host_impl(c, data, data_block_stride, parity, parity_block_stride, S, nblocks, chk);
+    // the fallback, as rsmi_heal's
+    return launch_heal_rows(c, plan, heal_pair_rows_kernel(), "rs_heal_pair_rows_kernel", rows, out, 2, stream);
 }
 
 }  // namespace
@@ -236,14 +132,11 @@ extern "C" {
 int rsmi_heal_pair_batch_dev(rsmi_ctx* c, uint8_t* d_data, size_t data_shard_stride, size_t data_block_stride,
                              uint8_t* d_parity, size_t parity_shard_stride, size_t parity_block_stride, size_t S,
                              size_t nblocks, int32_t* d_pair_out, uint32_t* d_bad_out, void* stream) try {
-    int rc = check_stripe_dev_args(c, d_data, data_shard_stride, d_parity, parity_shard_stride, S, d_pair_out);
-    if (rc) return rc;
-    if (nblocks == 0) return RSMI_OK;
-    std::shared_ptr<Plan> plan;
-    std::unique_lock<std::mutex> lock;
-    if ((rc = begin_stripe_dev_call(c, lock, plan))) return rc;
-    return launch_heal_pair(c, *plan, d_data, data_shard_stride, data_block_stride, d_parity, parity_shard_stride,
-                            parity_block_stride, S, nblocks, d_pair_out, d_bad_out, static_cast<hipStream_t>(stream));
+    return stripe_dev_call(
+        c, d_data, data_shard_stride, data_block_stride, d_parity, parity_shard_stride, parity_block_stride, S, nblocks,
+        d_pair_out, [&](const Plan& plan, const StripeRows& rows) {
+            return launch_heal_pair(c, plan, rows, d_pair_out, d_bad_out, static_cast<hipStream_t>(stream));
+        });
 } catch (...) {
     return rsmi::impl::exception_status();
 }
@@ -251,21 +144,14 @@ int rsmi_heal_pair_batch_dev(rsmi_ctx* c, uint8_t* d_data, size_t data_shard_str
 int rsmi_heal_pair_batch_host(rsmi_ctx* c, uint8_t* data, size_t data_block_stride, uint8_t* parity,
                               size_t parity_block_stride, size_t S, size_t nblocks, int32_t* pair_out,
                               uint32_t* bad_out) try {
-    return heal_pair_host_impl(c, data, data_block_stride, parity, parity_block_stride, S, nblocks, pair_out, bad_out);
+    return verdicts_host_impl(c, data, data_block_stride, parity, parity_block_stride, S, nblocks, 2, launch_heal_pair,
+                              pair_out, bad_out, data, parity);
 } catch (...) {
     return rsmi::impl::exception_status();
 }
 
 int rsmi_heal_pair(rsmi_ctx* c, uint8_t* shards, size_t S, int pair_out[2]) try {
-    if (!c || !shards || !pair_out) return RSMI_ERR_INVALID_ARG;
-    if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
-    const size_t k = size_t(c->k), m = size_t(c->m);
-    int32_t v[2] = {RSMI_LOCATE_UNKNOWN, RSMI_LOCATE_UNKNOWN};
-    int rc = heal_pair_host_impl(c, shards, k * S, shards + k * S, m * S, S, 1, v, nullptr);
-    if (rc) return rc;
-    pair_out[0] = int(v[0]);
-    pair_out[1] = int(v[1]);
-    return RSMI_OK;
+    return verdicts_one_block(c, shards, S, 2, launch_heal_pair, pair_out, shards);
 } catch (...) {
     return rsmi::impl::exception_status();
 }

@@ -4,9 +4,10 @@
 //   rsmi_crc.cpp       datanode CRC-16 on the GPU (separate pass and fused into the encode); the rows
 //                      passes over named rows (rsmi_crc_named_rows_dev)
 //   rsmi_coalesce.cpp  group commit of concurrent single-block calls
-//   rsmi_verify.cpp    Encoder.Verify: stored parity checked against the data rows; what the three
-//                      stripe checks share: the layout test, the tile launch, the scratch-encode
-//                      fallback, the host paths, the entry points' checks and prologue
+//   rsmi_verify.cpp    Encoder.Verify: stored parity checked against the data rows; what the six
+//                      stripe calls share: the rows' layout test, the tile launch and its label,
+//                      the scratch-encode fallback, the host paths with their results buffer and
+//                      write-back leg, the verdict calls' host entries, the entry points' checks
 //   rsmi_locate.cpp    rsmi_locate: the shard that breaks a stripe, from Verify's syndromes
 //   rsmi_heal.cpp      rsmi_heal: locate, then the named shard rewritten on the same stream
 //   rsmi_mixed.cpp     rsmi_reconstruct_mixed_*: a batch whose blocks each have their own erasure pattern
@@ -293,9 +294,32 @@ int reconstruct_host_impl(rsmi_ctx* c, uint8_t* shards, size_t block_stride, siz
 // The layout of a stripe's rows (rsmi_verify.cpp), which picks the tile kernels' form: 16-byte
 // aligned, unaligned windows (UA), or neither (the scratch-encode fallback).
 enum class StripeLayout { kAligned, kUA, kNeither };
-StripeLayout stripe_layout(const uint8_t* data, uint64_t data_rs, uint64_t data_bs, const uint8_t* parity,
-                           uint64_t parity_rs, uint64_t parity_bs, uint64_t S);
-// Encoder.Verify of nblocks blocks (rsmi_verify.cpp; caller holds ctx->mu): bad[b*m + j], device
+// The rows a call over stored stripes runs on: the first block's data and parity rows, their row
+// and block strides in bytes, the shard size and the number of blocks.  Every launch function of
+// the stripe calls takes one.  The rows are const, as Verify reads them; the healers, which
+// rewrite rows, cast where their rows kernels' arguments are built (launch_heal_rows).
+struct StripeRows {
+    const uint8_t* data = nullptr;
+    uint64_t data_rs = 0, data_bs = 0;
+    const uint8_t* parity = nullptr;
+    uint64_t parity_rs = 0, parity_bs = 0;
+    uint64_t S = 0, nblocks = 0;
+    // blocks [b0, b0 + nb): the one place where a block index meets a block stride
+    StripeRows from(uint64_t b0, uint64_t nb) const {
+        StripeRows r = *this;
+        r.data += b0 * data_bs;
+        r.parity += b0 * parity_bs;
+        r.nblocks = nb;
+        return r;
+    }
+    StripeLayout layout() const;
+};
+// A tile's kernel in a stripe call's table on a layout (null: the shape has none, or the layout is
+// kNeither), and the end of a tile launch: last_kernel's "rs_<name>_kernel<K=..,MT=..>[,UA]" set,
+// the status of the launches returned.
+void* stripe_kernel(const StripeKernelTable& table, StripeLayout layout, const DevTile& t);
+int tiles_launched(rsmi_ctx* c, const char* name, StripeLayout layout, const DevTile& t);
+// Encoder.Verify of rows.nblocks blocks (rsmi_verify.cpp; caller holds ctx->mu): bad[b*m + j], device
 // memory, zeroed here on the stream, then non-zero where stored parity row j of block b differs
 // from the encode of the block's data rows.  Stream-ordered, no synchronisation.
 // loc (rsmi_locate.cpp): where the shape has an rs_locate_kernel, that kernel runs in the place of
@@ -307,34 +331,38 @@ struct LocateFuse {
     uint32_t* cand = nullptr;
     StripeLayout fused = StripeLayout::kNeither;
 };
-int launch_verify(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
-                  const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks,
-                  uint32_t* bad, hipStream_t stream, LocateFuse* loc = nullptr);
-// rsmi_scrub of nblocks blocks (rsmi_scrub.cpp; caller holds ctx->mu): launch_verify's flags in
+int launch_verify(rsmi_ctx* c, const Plan& plan, const StripeRows& rows, uint32_t* bad, hipStream_t stream,
+                  LocateFuse* loc = nullptr);
+// rsmi_scrub of rows.nblocks blocks (rsmi_scrub.cpp; caller holds ctx->mu): launch_verify's flags in
 // bad[b*m + j] and R(row) of every data and parity row over bytes [0, S) in raw[b*(k+m) + r], data
 // rows first, both device memory, from one read of the rows (rs_scrub_mfma_kernel and the records'
 // combine) or, for shapes without that kernel, from launch_verify and launch_crc in turn.
 // Stream-ordered, no synchronisation unless the stream's record scratch grows.
-int launch_scrub(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
-                 const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks,
-                 uint32_t* bad, uint32_t* raw, hipStream_t stream);
-// One tile's rs_verify_kernel fn over nblocks blocks, or (rplan given) its rs_locate_kernel or
-// rs_heal_kernel: one tile per wave unless waves_per_cu caps the grid, in launches whose tile
-// count fits 32 bits.  words: the last kernel argument, one 32-bit word per block: the candidates
-// of rs_locate_kernel, the verdicts of rs_heal_kernel (which takes no bad).
-int launch_stripe_tiles(rsmi_ctx* c, void* fn, const DevTile& t, const uint8_t* data, uint64_t data_rs,
-                        uint64_t data_bs, const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S,
-                        uint64_t nblocks, uint32_t* bad, const RsPlanDev* rplan, void* words, hipStream_t stream);
+int launch_scrub(rsmi_ctx* c, const Plan& plan, const StripeRows& rows, uint32_t* bad, uint32_t* raw,
+                 hipStream_t stream);
+// One tile's kernel fn of a stripe call's table over the rows' blocks: one tile per wave unless
+// waves_per_cu caps the grid, in launches whose tile count fits 32 bits.  The tile kernels share
+// rs_verify_kernel's parameters and, behind them, a plan (rplan) and a second per-block output.
+// Each of the two per-block outputs moves on by its own words per block from launch to launch:
+//   bad    bad_wpb = m: Verify's flags; pair_words(n): the pair words of rs_locate_pair_kernel;
+//          null for the heal kernels, which take none
+//   words  words_wpb = 1: the candidates of rs_locate_kernel, the verdicts rs_heal_kernel and
+//          rs_locate_pair_kernel read; 2: the pair verdicts of rs_heal_pair_kernel; null for
+//          rs_verify_kernel
+int launch_stripe_tiles(rsmi_ctx* c, void* fn, const DevTile& t, const StripeRows& rows, uint32_t* bad,
+                        uint64_t bad_wpb, const RsPlanDev* rplan, void* words, uint64_t words_wpb, hipStream_t stream);
 // The stream's entry of a per-stream scratch map (caller holds ctx->mu): verify_scratch, the
 // fallback's encoded rows; locate_scratch; scrub_scratch.  Past 32 streams the device is drained once and every
 // stream's scratch freed.
 rsmi_ctx::VerifyScratch& stream_scratch(std::map<hipStream_t, rsmi_ctx::VerifyScratch>& map, hipStream_t st);
 // The fallback of the shapes without a tile kernel: the encode of the data rows into the stream's
 // verify_scratch (16-byte-aligned rows), at most 64 MiB of scratch rows at a time, and per chunk
-// of nb blocks from block b0 the caller's byte-granular launch, before the next encode reuses them.
-using ScratchRowsFn = std::function<int(uint64_t b0, uint64_t nb, const uint8_t* enc, uint64_t enc_rs, uint64_t enc_bs)>;
-int encode_into_scratch(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
-                        uint64_t S, uint64_t nblocks, hipStream_t stream, const ScratchRowsFn& fn);
+// of blocks from block b0 (sub: their rows, a copy whose members a kernel argument array may
+// point to) the caller's byte-granular launch, before the next encode reuses them.
+using ScratchRowsFn =
+    std::function<int(uint64_t b0, StripeRows sub, const uint8_t* enc, uint64_t enc_rs, uint64_t enc_bs)>;
+int encode_into_scratch(rsmi_ctx* c, const Plan& plan, const StripeRows& rows, hipStream_t stream,
+                        const ScratchRowsFn& fn);
 // The argument checks of the *_batch_dev entries and of the host impls (out: the output that must
 // be given), and the device entries' prologue: ctx->mu taken into lock, the device bound, the
 // encode plan (declared before lock by the caller, so it outlives the lock).
@@ -343,14 +371,29 @@ int check_stripe_dev_args(const rsmi_ctx* c, const void* d_data, size_t data_sha
 int check_stripe_host_args(const rsmi_ctx* c, const void* data, size_t data_block_stride, const void* parity,
                            size_t parity_block_stride, size_t S, const void* out);
 int begin_stripe_dev_call(rsmi_ctx* c, std::unique_lock<std::mutex>& lock, std::shared_ptr<Plan>& plan);
-// What a host-memory call runs over stored stripes (Encoder.Verify, rsmi_locate): verify_host_impl
-// stages or uploads the rows on one of rsmi_verify_batch_host's three paths and calls
+// A *_batch_dev entry between its try and its catch: the checks, nothing to do for no blocks, the
+// prologue, then the entry's own launch(plan, rows) under the lock.
+template <class Launch>
+int stripe_dev_call(rsmi_ctx* c, const uint8_t* d_data, size_t data_shard_stride, size_t data_block_stride,
+                    const uint8_t* d_parity, size_t parity_shard_stride, size_t parity_block_stride, size_t S,
+                    size_t nblocks, const void* out, const Launch& launch) {
+    int rc = check_stripe_dev_args(c, d_data, data_shard_stride, d_parity, parity_shard_stride, S, out);
+    if (rc) return rc;
+    if (nblocks == 0) return RSMI_OK;
+    std::shared_ptr<Plan> plan;
+    std::unique_lock<std::mutex> lock;
+    if ((rc = begin_stripe_dev_call(c, lock, plan))) return rc;
+    return launch(*plan, StripeRows{d_data, data_shard_stride, data_block_stride, d_parity, parity_shard_stride,
+                                    parity_block_stride, S, nblocks});
+}
+// What a host-memory call runs over stored stripes: verify_host_impl stages or uploads the rows on
+// one of rsmi_verify_batch_host's three paths and calls
 //   prepare()  once, under ctx->mu with the device bound: the call's device result buffers
-//   launch()   per staged range of nb blocks from block b0, rows visible to the device
+//   launch()   per staged range of blocks from block b0, its rows visible to the device
 //   fetch(st)  the results to the caller's memory: queued on st, which the caller then
 //              synchronises, or (st null, every stream idle) copied synchronously
-// rsmi_heal and rsmi_heal_pair alone write rows, so they alone set the write-back leg (unset: no
-// step is added):
+// stripe_results sets prepare and fetch.  rsmi_heal and rsmi_heal_pair alone write rows, so they
+// alone set the write-back leg (stripe_write_back; unset: no step is added):
 //   small_done(sd, sp)          the small staged call, after its synchronisation: the page-locked
 //                               copies of the data blocks (k*S apart) and of the parity blocks
 //                               (m*S apart), null for a half that was not staged
@@ -358,36 +401,59 @@ int begin_stripe_dev_call(rsmi_ctx* c, std::unique_lock<std::mutex>& lock, std::
 //                               b0 .. b0+nb are overwritten by a later chunk, and at the end
 struct StripeCheck {
     std::function<int()> prepare;
-    std::function<int(const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs, const uint8_t* parity,
-                      uint64_t parity_rs, uint64_t parity_bs, uint64_t nb, uint64_t b0, hipStream_t st)>
-        launch;
+    std::function<int(const Plan& plan, const StripeRows& rows, uint64_t b0, hipStream_t st)> launch;
     std::function<int(hipStream_t st)> fetch;
     std::function<int(const uint8_t* sd, const uint8_t* sp)> small_done;
     std::function<int(Staging& st, uint64_t b0, uint64_t nb, size_t Sp)> chunk_done;
 };
 int verify_host_impl(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
                      size_t parity_block_stride, size_t S, size_t nblocks, const StripeCheck& chk);
-// The device result buffer of a host call, in ctx->d_vbad: the flags of nblocks blocks, then (locate
-// and heal: culprit_out given) their verdicts.  stripe_results sets chk.prepare, which reserves it
-// and sets r, and chk.fetch, which copies out what the caller takes.  r must outlive chk.
+// The device result buffer of a host call, in ctx->d_vbad: the flags of nblocks blocks, then W
+// 32-bit words per block of the call's second output: none for Verify, the verdict of locate and
+// heal, the two of locate pair and heal pair, the k + m raws of scrub.  stripe_results sets
+// chk.prepare, which reserves the buffer and sets r, and chk.fetch, which copies the words to
+// words_out and, when bad_out is given, the flags there.  r must outlive chk.
 struct StripeResults {
     uint32_t* d_bad = nullptr;
-    int32_t* d_culprit = nullptr;
+    uint32_t* d_words = nullptr;
+    int32_t* verdicts() const { return reinterpret_cast<int32_t*>(d_words); }
 };
-void stripe_results(rsmi_ctx* c, size_t nblocks, int32_t* culprit_out, uint32_t* bad_out, StripeResults& r,
+void stripe_results(rsmi_ctx* c, size_t nblocks, size_t W, void* words_out, uint32_t* bad_out, StripeResults& r,
                     StripeCheck& chk);
-// rsmi_locate of nblocks blocks (rsmi_locate.cpp; caller holds ctx->mu): verdicts culprit[b] and,
+// The write-back leg of the healers' host calls: sets chk.small_done and chk.chunk_done, which
+// return the rows that the W verdict words of every block name (verdict_out, r.verdicts()) to where
+// the caller keeps them, and nothing else.
+void stripe_write_back(rsmi_ctx* c, uint8_t* data, size_t data_block_stride, uint8_t* parity,
+                       size_t parity_block_stride, size_t S, size_t nblocks, size_t W, int32_t* verdict_out,
+                       const StripeResults& r, StripeCheck& chk);
+// The host entries of the four calls that return verdicts (locate, heal, locate pair, heal pair),
+// which differ in W, the verdict words per block, in their launch (blocks' rows, verdicts and
+// flags in device memory, stream-ordered) and in whether they write rows: the healers give their
+// rows once more, writable (home_data, home_parity), and get the write-back leg.
+// verdicts_one_block is the block-of-one wrapper around it: k + m rows S apart, out[W].
+using VerdictLaunch = int (*)(rsmi_ctx* c, const Plan& plan, const StripeRows& rows, int32_t* verdicts, uint32_t* bad,
+                              hipStream_t stream);
+int verdicts_host_impl(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
+                       size_t parity_block_stride, size_t S, size_t nblocks, size_t W, VerdictLaunch launch,
+                       int32_t* verdict_out, uint32_t* bad_out, uint8_t* home_data = nullptr,
+                       uint8_t* home_parity = nullptr);
+int verdicts_one_block(rsmi_ctx* c, const uint8_t* shards, size_t S, size_t W, VerdictLaunch launch, int* out,
+                       uint8_t* home = nullptr);
+// rsmi_locate of rows.nblocks blocks (rsmi_locate.cpp; caller holds ctx->mu): verdicts culprit[b] and,
 // when bad is given, Verify's flags, device memory, stream-ordered.  fused: the layout
 // rs_locate_kernel ran on (kNeither: m = 1, or the encode into scratch and rs_locate_rows_kernel).
-int launch_locate(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
-                  const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks,
-                  int32_t* culprit, uint32_t* bad, hipStream_t stream, StripeLayout* fused = nullptr);
+int launch_locate(rsmi_ctx* c, const Plan& plan, const StripeRows& rows, int32_t* culprit, uint32_t* bad,
+                  hipStream_t stream, StripeLayout* fused = nullptr);
 // rsmi_heal's launch behind launch_locate's verdicts (rsmi_heal.cpp; caller holds ctx->mu, m >= 2):
 // rs_heal_kernel on the layout fused names, or the encode into scratch and rs_heal_rows_kernel.
-int launch_heal_named(rsmi_ctx* c, const Plan& plan, StripeLayout fused, uint8_t* data, uint64_t data_rs,
-                      uint64_t data_bs, uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S,
-                      uint64_t nblocks, int32_t* culprit, hipStream_t stream);
-// rsmi_locate_pair of nblocks blocks (rsmi_pair.cpp; caller holds ctx->mu): two verdict words per
+int launch_heal_named(rsmi_ctx* c, const Plan& plan, StripeLayout fused, const StripeRows& rows, int32_t* culprit,
+                      hipStream_t stream);
+// The healers' fallback (rsmi_heal.cpp): the data rows encoded into scratch, chunk by chunk, and
+// behind each chunk's encode the byte-granular kernel (rs_heal_rows_kernel, rs_heal_pair_rows_kernel:
+// one parameter list), which rewrites the rows that the W verdict words of a block name.
+int launch_heal_rows(rsmi_ctx* c, const Plan& plan, void* kernel, const char* label, const StripeRows& rows,
+                     const int32_t* verdict, uint64_t W, hipStream_t stream);
+// rsmi_locate_pair of rows.nblocks blocks (rsmi_pair.cpp; caller holds ctx->mu): two verdict words per
 // block in out and, when bad is given, Verify's flags, device memory, stream-ordered.  info: the
 // layout rs_locate_kernel ran on (kNeither: the fallback) and rsmi_locate's verdicts, one word per
 // block in the stream's scratch, valid until the stream's next stripe call.
@@ -395,9 +461,8 @@ struct PairLaunch {
     StripeLayout fused = StripeLayout::kNeither;
     int32_t* culprit = nullptr;
 };
-int launch_locate_pair(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
-                       const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks,
-                       int32_t* out, uint32_t* bad, hipStream_t stream, PairLaunch* info = nullptr);
+int launch_locate_pair(rsmi_ctx* c, const Plan& plan, const StripeRows& rows, int32_t* out, uint32_t* bad,
+                       hipStream_t stream, PairLaunch* info = nullptr);
 // the ratio matrix's plan "L" (output slot 0: inv(M[k][c])) and the byte-granular kernels' tables
 // (ctx->d_locate_tbl: log | exp | R | inv(M[k][c])), both built on first use
 int ratio_plan(rsmi_ctx* c, std::shared_ptr<Plan>& out);

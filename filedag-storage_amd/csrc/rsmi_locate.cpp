@@ -5,6 +5,7 @@
 // other syndrome is zero.  rs_locate_kernel (rs_locate_kernels.hip) forms flags and candidates in
 // one pass over the k + m rows; shapes it is not built for take Verify's launch for the flags,
 // the encode into scratch and rs_locate_rows_kernel; rs_locate_verdict_kernel ends every launch.
+// The host entries are verdicts_host_impl's (rsmi_verify.cpp), one verdict word per block.
 
 #include "rsmi_impl.hpp"
 
@@ -69,11 +70,11 @@ int ensure_locate_tables(rsmi_ctx* c) {
 // is given, Verify's flags bad[b*m + j], both device memory.  Stream-ordered; the candidate words
 // (and the flags, when the caller takes none) live in the stream's scratch.  fused (rsmi_heal.cpp):
 // the layout rs_locate_kernel ran on (kNeither: m = 1 or the fallback).
-int launch_locate(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
-                  const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks,
-                  int32_t* culprit, uint32_t* bad, hipStream_t stream, StripeLayout* fused) {
+int launch_locate(rsmi_ctx* c, const Plan& plan, const StripeRows& rows, int32_t* culprit, uint32_t* bad,
+                  hipStream_t stream, StripeLayout* fused) {
     if (fused) *fused = StripeLayout::kNeither;
-    if (nblocks == 0 || S == 0) return RSMI_OK;
+    const uint64_t nblocks = rows.nblocks;
+    if (nblocks == 0 || rows.S == 0) return RSMI_OK;
     const uint64_t k = uint64_t(c->k), m = uint64_t(c->m);
     uint32_t n32 = uint32_t(c->n), m32 = uint32_t(m), words = (n32 + 31u) / 32u;
     const size_t cand_bytes = nblocks * words * sizeof(uint32_t);
@@ -85,8 +86,7 @@ int launch_locate(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t d
 
     if (m == 1) {
         // every shard explains any damage: the verdict follows from Verify's flag alone
-        if ((rc = launch_verify(c, plan, data, data_rs, data_bs, parity, parity_rs, parity_bs, S, nblocks, bad, stream)))
-            return rc;
+        if ((rc = launch_verify(c, plan, rows, bad, stream))) return rc;
         cand = nullptr;
     } else {
         HIP_TRY(hipMemsetAsync(cand, 0xFF, cand_bytes, stream));
@@ -99,9 +99,7 @@ int launch_locate(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t d
             loc.rplan = rp->tiles[0].dev;
             loc.cand = cand;
         }
-        if ((rc = launch_verify(c, plan, data, data_rs, data_bs, parity, parity_rs, parity_bs, S, nblocks, bad, stream,
-                                rp ? &loc : nullptr)))
-            return rc;
+        if ((rc = launch_verify(c, plan, rows, bad, stream, rp ? &loc : nullptr))) return rc;
         if (fused) *fused = loc.fused;
         if (loc.fused == StripeLayout::kNeither) {
             // m > 4, K > 16 or not instantiated, unaligned rows shorter than 16 bytes: Verify's
@@ -110,17 +108,16 @@ int launch_locate(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t d
             // The correctness path of rare shapes.
             if ((rc = ensure_locate_tables(c))) return rc;
             rc = encode_into_scratch(
-                c, plan, data, data_rs, data_bs, S, nblocks, stream,
-                [&](uint64_t b0, uint64_t nb, const uint8_t* enc, uint64_t enc_rs, uint64_t enc_bs) -> int {
-                    const uint8_t* parb = parity + b0 * parity_bs;
+                c, plan, rows, stream,
+                [&](uint64_t b0, StripeRows r, const uint8_t* enc, uint64_t enc_rs, uint64_t enc_bs) -> int {
                     uint32_t k32 = uint32_t(k);
                     const uint32_t* badb = bad + b0 * m;
                     const uint8_t* tbl = c->d_locate_tbl;
                     uint32_t* candb = cand + b0 * words;
-                    const uint32_t gx = uint32_t(std::min<uint64_t>((S + kWG - 1) / kWG, 4096));
-                    const uint32_t gy = uint32_t(std::min<uint64_t>(nb, 65535));
-                    void* args[] = {&enc, &enc_rs, &enc_bs, &parb, &parity_rs, &parity_bs, &S,
-                                    &k32, &m32,    &nb,     &badb, &tbl,       &candb};
+                    const uint32_t gx = uint32_t(std::min<uint64_t>((r.S + kWG - 1) / kWG, 4096));
+                    const uint32_t gy = uint32_t(std::min<uint64_t>(r.nblocks, 65535));
+                    void* args[] = {&enc, &enc_rs, &enc_bs,    &r.parity, &r.parity_rs, &r.parity_bs, &r.S,
+                                    &k32, &m32,    &r.nblocks, &badb,     &tbl,         &candb};
                     HIP_TRY(hipLaunchKernel(locate_rows_kernel(), dim3(gx, gy), dim3(kWG), args, size_t(m * k),
                                             stream));
                     return RSMI_OK;
@@ -140,22 +137,10 @@ int launch_locate(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t d
 
 namespace {
 
-// Host-memory locate on Verify's host paths (verify_host_impl): flags and verdicts live in the
-// context's device result buffer, flags first.
-int locate_host_impl(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
-                     size_t parity_block_stride, size_t S, size_t nblocks, int32_t* culprit_out, uint32_t* bad_out) {
-    if (int rc = check_stripe_host_args(c, data, data_block_stride, parity, parity_block_stride, S, culprit_out))
-        return rc;
-    if (nblocks == 0) return RSMI_OK;
-    const size_t m = size_t(c->m);
-    StripeResults r;
-    StripeCheck chk;
-    stripe_results(c, nblocks, culprit_out, bad_out, r, chk);
-    chk.launch = [&](const Plan& plan, const uint8_t* d, uint64_t d_rs, uint64_t d_bs, const uint8_t* p, uint64_t p_rs,
-                     uint64_t p_bs, uint64_t nb, uint64_t b0, hipStream_t st) -> int {
-        return launch_locate(c, plan, d, d_rs, d_bs, p, p_rs, p_bs, S, nb, r.d_culprit + b0, r.d_bad + b0 * m, st);
-    };
-    return verify_host_impl(c, data, data_block_stride, parity, parity_block_stride, S, nblocks, chk);
+// the host entries' launch (verdicts_host_impl): one verdict word per block
+int locate_launch(rsmi_ctx* c, const Plan& plan, const StripeRows& rows, int32_t* culprit, uint32_t* bad,
+                  hipStream_t stream) {
+    return launch_locate(c, plan, rows, culprit, bad, stream);
 }
 
 }  // namespace
@@ -168,14 +153,11 @@ extern "C" {
 int rsmi_locate_batch_dev(rsmi_ctx* c, const uint8_t* d_data, size_t data_shard_stride, size_t data_block_stride,
                           const uint8_t* d_parity, size_t parity_shard_stride, size_t parity_block_stride, size_t S,
                           size_t nblocks, int32_t* d_culprit_out, uint32_t* d_bad_out, void* stream) try {
-    int rc = check_stripe_dev_args(c, d_data, data_shard_stride, d_parity, parity_shard_stride, S, d_culprit_out);
-    if (rc) return rc;
-    if (nblocks == 0) return RSMI_OK;
-    std::shared_ptr<Plan> plan;
-    std::unique_lock<std::mutex> lock;
-    if ((rc = begin_stripe_dev_call(c, lock, plan))) return rc;
-    return launch_locate(c, *plan, d_data, data_shard_stride, data_block_stride, d_parity, parity_shard_stride,
-                         parity_block_stride, S, nblocks, d_culprit_out, d_bad_out, static_cast<hipStream_t>(stream));
+    return stripe_dev_call(
+        c, d_data, data_shard_stride, data_block_stride, d_parity, parity_shard_stride, parity_block_stride, S, nblocks,
+        d_culprit_out, [&](const Plan& plan, const StripeRows& rows) {
+            return launch_locate(c, plan, rows, d_culprit_out, d_bad_out, static_cast<hipStream_t>(stream));
+        });
 } catch (...) {
     return rsmi::impl::exception_status();
 }
@@ -183,20 +165,14 @@ int rsmi_locate_batch_dev(rsmi_ctx* c, const uint8_t* d_data, size_t data_shard_
 int rsmi_locate_batch_host(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
                            size_t parity_block_stride, size_t S, size_t nblocks, int32_t* culprit_out,
                            uint32_t* bad_out) try {
-    return locate_host_impl(c, data, data_block_stride, parity, parity_block_stride, S, nblocks, culprit_out, bad_out);
+    return verdicts_host_impl(c, data, data_block_stride, parity, parity_block_stride, S, nblocks, 1, locate_launch,
+                              culprit_out, bad_out);
 } catch (...) {
     return rsmi::impl::exception_status();
 }
 
 int rsmi_locate(rsmi_ctx* c, const uint8_t* shards, size_t S, int* culprit_out) try {
-    if (!c || !shards || !culprit_out) return RSMI_ERR_INVALID_ARG;
-    if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
-    const size_t k = size_t(c->k), m = size_t(c->m);
-    int32_t v = RSMI_LOCATE_UNKNOWN;
-    int rc = locate_host_impl(c, shards, k * S, shards + k * S, m * S, S, 1, &v, nullptr);
-    if (rc) return rc;
-    *culprit_out = int(v);
-    return RSMI_OK;
+    return verdicts_one_block(c, shards, S, 1, locate_launch, culprit_out);
 } catch (...) {
     return rsmi::impl::exception_status();
 }

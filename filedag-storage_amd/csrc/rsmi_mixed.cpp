@@ -116,7 +116,7 @@ int launch_mixed(rsmi_ctx* c, const MixedBatch& mb, uint8_t* base, uint64_t rs, 
     const bool crcs = d16 || d32;
     const size_t n = size_t(c->n), npat = mb.keys.size();
     // launch_plan's layout test, the rows being read and written in place
-    const StripeLayout layout = stripe_layout(base, rs, bs, base, rs, bs, S);
+    const StripeLayout layout = StripeRows{base, rs, bs, base, rs, bs, S, nb}.layout();
     const bool aligned = layout == StripeLayout::kAligned;
     const uint64_t cpb = (S + 15) / 16;
     const uint64_t tpb = (cpb + uint64_t(kWave) - 1) / uint64_t(kWave);

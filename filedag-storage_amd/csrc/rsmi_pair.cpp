@@ -5,12 +5,10 @@
 // the syndromes of the blocks whose verdict is UNKNOWN; rs_locate_pair_verdict_kernel ends every
 // call.  Shapes without an rs_locate_kernel encode the data rows into scratch once more, chunk by
 // chunk, and run the byte-granular rs_locate_pair_rows_kernel.  m <= 2 names no pair: rsmi_locate's
-// verdicts are widened to two words and nothing else is launched.  The host paths are Verify's
-// (verify_host_impl).
+// verdicts are widened to two words and nothing else is launched.  The host entries are
+// verdicts_host_impl's (rsmi_verify.cpp), two verdict words per block.
 
 #include "rsmi_impl.hpp"
-
-#include <limits>
 
 using namespace rsmi;
 using namespace rsmi::impl;
@@ -116,11 +114,11 @@ int launch_pair_verdict(const int32_t* culprit, const uint32_t* pairw, uint32_t 
 // locate_scratch holds, behind launch_locate's candidate words, rsmi_locate's verdicts, the pair
 // words and (when the caller takes none) the flags.  info (rsmi_heal_pair.cpp): the layout
 // rs_locate_kernel ran on and where rsmi_locate's verdicts lie.
-int launch_locate_pair(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
-                       const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks,
-                       int32_t* out, uint32_t* bad, hipStream_t stream, PairLaunch* info) {
+int launch_locate_pair(rsmi_ctx* c, const Plan& plan, const StripeRows& rows, int32_t* out, uint32_t* bad,
+                       hipStream_t stream, PairLaunch* info) {
     if (info) *info = PairLaunch{};
-    if (nblocks == 0 || S == 0) return RSMI_OK;
+    const uint64_t nblocks = rows.nblocks;
+    if (nblocks == 0 || rows.S == 0) return RSMI_OK;
     const uint64_t m = uint64_t(c->m);
     const uint32_t n32 = uint32_t(c->n);
     // a shape rs_locate_kernel may run on has pair words (n <= 20); the fallback needs none
@@ -138,9 +136,7 @@ int launch_locate_pair(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint6
     if (!bad) bad = pairw + nblocks * words;
 
     StripeLayout fused = StripeLayout::kNeither;
-    rc = launch_locate(c, plan, data, data_rs, data_bs, parity, parity_rs, parity_bs, S, nblocks, culprit, bad, stream,
-                       &fused);
-    if (rc) return rc;
+    if ((rc = launch_locate(c, plan, rows, culprit, bad, stream, &fused))) return rc;
     if (info) {
         info->fused = fused;
         info->culprit = culprit;
@@ -151,28 +147,16 @@ int launch_locate_pair(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint6
         return hip_status(hipGetLastError());
     }
     if (fused != StripeLayout::kNeither) {
-        const bool aligned = fused == StripeLayout::kAligned;
         const DevTile& t = plan.tiles[0];
-        void* fn = (aligned ? pair_kernels().fn : pair_kernels().ua)[t.K][t.MT];
+        void* fn = stripe_kernel(pair_kernels(), fused, t);
         if (!fn || !words) return RSMI_ERR_DEVICE;  // a locate kernel without its pair kernel: a build error
         std::shared_ptr<Plan> pp;
         if ((rc = pair_plan(c, pp))) return rc;
         HIP_TRY(hipMemsetAsync(pairw, 0xFF, pair_bytes, stream));
-        // launch_stripe_tiles' own split (a launch's tile count fits 32 bits), made here: it moves
-        // its one-word-per-block argument on, and the pair words are several per block
-        const uint64_t tpb = ((S + 15) / 16 + uint64_t(kWave) - 1) / uint64_t(kWave);
-        const uint64_t max_blocks = std::max<uint64_t>(1, (uint64_t(1) << 31) / tpb);
-        for (uint64_t b0 = 0; b0 < nblocks; b0 += max_blocks) {
-            const uint64_t nb = std::min(max_blocks, nblocks - b0);
-            rc = launch_stripe_tiles(c, fn, t, data + b0 * data_bs, data_rs, data_bs, parity + b0 * parity_bs, parity_rs,
-                                     parity_bs, S, nb, pairw + b0 * words, pp->tiles[0].dev, culprit + b0, stream);
-            if (rc) return rc;
-        }
+        // the pair words in the flags' place, rsmi_locate's verdicts in the candidates'
+        if ((rc = launch_stripe_tiles(c, fn, t, rows, pairw, words, pp->tiles[0].dev, culprit, 1, stream))) return rc;
         if ((rc = launch_pair_verdict(culprit, pairw, n32, words, nblocks, out, stream))) return rc;
-        char buf[96];
-        std::snprintf(buf, sizeof buf, "rs_locate_pair_kernel<K=%d,MT=%d>%s", t.K, t.MT, aligned ? "" : ",UA");
-        set_last_kernel(c, buf);
-        return hip_status(hipGetLastError());
+        return tiles_launched(c, "locate_pair", fused, t);
     }
     // The fallback's scratch rows are gone (every 64 MiB chunk reuses them): the verdicts are
     // widened, then the data rows are encoded again, chunk by chunk, and each chunk's UNKNOWN
@@ -180,16 +164,15 @@ int launch_locate_pair(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint6
     if ((rc = launch_pair_verdict(culprit, nullptr, n32, 0, nblocks, out, stream))) return rc;
     if ((rc = ensure_locate_tables(c))) return rc;
     rc = encode_into_scratch(
-        c, plan, data, data_rs, data_bs, S, nblocks, stream,
-        [&](uint64_t b0, uint64_t nb, const uint8_t* enc, uint64_t enc_rs, uint64_t enc_bs) -> int {
-            const uint8_t* parb = parity + b0 * parity_bs;
+        c, plan, rows, stream,
+        [&](uint64_t b0, StripeRows r, const uint8_t* enc, uint64_t enc_rs, uint64_t enc_bs) -> int {
             uint32_t k32 = uint32_t(c->k), m32 = uint32_t(c->m);
             const int32_t* verdict = culprit + b0;
             const uint8_t* tbl = c->d_locate_tbl;
             int32_t* outb = out + 2 * b0;
-            const uint32_t gx = uint32_t(std::min<uint64_t>(nb, 65535));
-            void* args[] = {&enc, &enc_rs, &enc_bs, &parb, &parity_rs, &parity_bs, &S,
-                            &k32, &m32,    &nb,     &verdict, &tbl,     &outb};
+            const uint32_t gx = uint32_t(std::min<uint64_t>(r.nblocks, 65535));
+            void* args[] = {&enc, &enc_rs, &enc_bs,    &r.parity, &r.parity_rs, &r.parity_bs, &r.S,
+                            &k32, &m32,    &r.nblocks, &verdict,  &tbl,         &outb};
             HIP_TRY(hipLaunchKernel(pair_rows_kernel(), dim3(gx), dim3(kWG), args, size_t(m32) * k32, stream));
             return RSMI_OK;
         });
@@ -200,40 +183,10 @@ int launch_locate_pair(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint6
 
 namespace {
 
-// Host-memory pair locate on Verify's host paths (verify_host_impl).  Launch and read-back are
-// this call's own: the context's device result buffer holds the flags, then two verdict words per
-// block.
-int locate_pair_host_impl(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
-                          size_t parity_block_stride, size_t S, size_t nblocks, int32_t* pair_out, uint32_t* bad_out) {
-    if (int rc = check_stripe_host_args(c, data, data_block_stride, parity, parity_block_stride, S, pair_out))
-        return rc;
-    if (nblocks == 0) return RSMI_OK;
-    const size_t m = size_t(c->m);
-    const size_t flag_bytes = nblocks * m * sizeof(uint32_t), verdict_bytes = 2 * nblocks * sizeof(int32_t);
-    uint32_t* d_bad = nullptr;
-    int32_t* d_pair = nullptr;
-    StripeCheck chk;
-    chk.prepare = [&]() -> int {
-        int rc = reserve(c->d_vbad, c->vbad_cap, flag_bytes + verdict_bytes);
-        d_bad = reinterpret_cast<uint32_t*>(c->d_vbad);
-        d_pair = reinterpret_cast<int32_t*>(d_bad + nblocks * m);
-        return rc;
-    };
-    chk.launch = [&](const Plan& plan, const uint8_t* d, uint64_t d_rs, uint64_t d_bs, const uint8_t* p, uint64_t p_rs,
-                     uint64_t p_bs, uint64_t nb, uint64_t b0, hipStream_t st) -> int {
-        return launch_locate_pair(c, plan, d, d_rs, d_bs, p, p_rs, p_bs, S, nb, d_pair + 2 * b0, d_bad + b0 * m, st);
-    };
-    chk.fetch = [&](hipStream_t st) -> int {
-        if (st) {
-            HIP_TRY(hipMemcpyAsync(pair_out, d_pair, verdict_bytes, hipMemcpyDeviceToHost, st));
-            if (bad_out) HIP_TRY(hipMemcpyAsync(bad_out, d_bad, flag_bytes, hipMemcpyDeviceToHost, st));
-        } else {
-            HIP_TRY(hipMemcpy(pair_out, d_pair, verdict_bytes, hipMemcpyDeviceToHost));
-            if (bad_out) HIP_TRY(hipMemcpy(bad_out, d_bad, flag_bytes, hipMemcpyDeviceToHost));
-        }
-        return RSMI_OK;
-    };
-    return verify_host_impl(c, data, data_block_stride, parity, parity_block_stride, S, nblocks, chk);
+// the host entries' launch (verdicts_host_impl): two verdict words per block
+int locate_pair_launch(rsmi_ctx* c, const Plan& plan, const StripeRows& rows, int32_t* out, uint32_t* bad,
+                       hipStream_t stream) {
+    return launch_locate_pair(c, plan, rows, out, bad, stream);
 }
 
 }  // namespace
@@ -246,14 +199,11 @@ extern "C" {
 int rsmi_locate_pair_batch_dev(rsmi_ctx* c, const uint8_t* d_data, size_t data_shard_stride, size_t data_block_stride,
                                const uint8_t* d_parity, size_t parity_shard_stride, size_t parity_block_stride,
                                size_t S, size_t nblocks, int32_t* d_pair_out, uint32_t* d_bad_out, void* stream) try {
-    int rc = check_stripe_dev_args(c, d_data, data_shard_stride, d_parity, parity_shard_stride, S, d_pair_out);
-    if (rc) return rc;
-    if (nblocks == 0) return RSMI_OK;
-    std::shared_ptr<Plan> plan;
-    std::unique_lock<std::mutex> lock;
-    if ((rc = begin_stripe_dev_call(c, lock, plan))) return rc;
-    return launch_locate_pair(c, *plan, d_data, data_shard_stride, data_block_stride, d_parity, parity_shard_stride,
-                              parity_block_stride, S, nblocks, d_pair_out, d_bad_out, static_cast<hipStream_t>(stream));
+    return stripe_dev_call(
+        c, d_data, data_shard_stride, data_block_stride, d_parity, parity_shard_stride, parity_block_stride, S, nblocks,
+        d_pair_out, [&](const Plan& plan, const StripeRows& rows) {
+            return launch_locate_pair(c, plan, rows, d_pair_out, d_bad_out, static_cast<hipStream_t>(stream));
+        });
 } catch (...) {
     return rsmi::impl::exception_status();
 }
@@ -261,22 +211,14 @@ int rsmi_locate_pair_batch_dev(rsmi_ctx* c, const uint8_t* d_data, size_t data_s
 int rsmi_locate_pair_batch_host(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride, const uint8_t* parity,
                                 size_t parity_block_stride, size_t S, size_t nblocks, int32_t* pair_out,
                                 uint32_t* bad_out) try {
-    return locate_pair_host_impl(c, data, data_block_stride, parity, parity_block_stride, S, nblocks, pair_out,
-                                 bad_out);
+    return verdicts_host_impl(c, data, data_block_stride, parity, parity_block_stride, S, nblocks, 2,
+                              locate_pair_launch, pair_out, bad_out);
 } catch (...) {
     return rsmi::impl::exception_status();
 }
 
 int rsmi_locate_pair(rsmi_ctx* c, const uint8_t* shards, size_t S, int pair_out[2]) try {
-    if (!c || !shards || !pair_out) return RSMI_ERR_INVALID_ARG;
-    if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
-    const size_t k = size_t(c->k), m = size_t(c->m);
-    int32_t v[2] = {RSMI_LOCATE_UNKNOWN, RSMI_LOCATE_UNKNOWN};
-    int rc = locate_pair_host_impl(c, shards, k * S, shards + k * S, m * S, S, 1, v, nullptr);
-    if (rc) return rc;
-    pair_out[0] = int(v[0]);
-    pair_out[1] = int(v[1]);
-    return RSMI_OK;
+    return verdicts_one_block(c, shards, S, 2, locate_pair_launch, pair_out);
 } catch (...) {
     return rsmi::impl::exception_status();
 }

@@ -4,7 +4,8 @@
 // of the datanode entry checksum (is each shard the bytes that were stored?).
 // rs_scrub_mfma_kernel (rs_scrub_kernels.hip) writes the flags and the units' CRC records, and
 // rs_crc16_combine_mfma_kernel turns the records into R(row); shapes without a scrub kernel run
-// Verify and the CRC-16 rows pass one after the other.  The host paths are verify_host_impl's.
+// Verify and the CRC-16 rows pass one after the other.  The host paths are verify_host_impl's, the
+// raws the second output of stripe_results.
 
 #include "rsmi_impl.hpp"
 
@@ -14,25 +15,23 @@ using namespace rsmi::impl;
 namespace rsmi {
 namespace impl {
 
-int launch_scrub(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t data_rs, uint64_t data_bs,
-                 const uint8_t* parity, uint64_t parity_rs, uint64_t parity_bs, uint64_t S, uint64_t nblocks,
-                 uint32_t* bad, uint32_t* raw, hipStream_t stream) {
+int launch_scrub(rsmi_ctx* c, const Plan& plan, const StripeRows& rows, uint32_t* bad, uint32_t* raw,
+                 hipStream_t stream) {
+    const uint64_t S = rows.S, nblocks = rows.nblocks;
     if (nblocks == 0 || S == 0) return RSMI_OK;
     const uint64_t k = uint64_t(c->k), m = uint64_t(c->m), n = k + m;
     int rc;
-    const StripeLayout layout = stripe_layout(data, data_rs, data_bs, parity, parity_rs, parity_bs, S);
-    const bool aligned = layout == StripeLayout::kAligned, ua = layout == StripeLayout::kUA;
-    void* fn = nullptr;
-    if (plan.tiles.size() == 1 && plan.tiles[0].K <= 16 && (aligned || ua))
-        fn = (aligned ? scrub_kernels().fn : scrub_kernels().ua)[plan.tiles[0].K][plan.tiles[0].MT];
+    const StripeLayout layout = rows.layout();
+    void* fn = plan.tiles.size() == 1 ? stripe_kernel(scrub_kernels(), layout, plan.tiles[0]) : nullptr;
     if (!fn) {
         // m > 4, a K without an rs_scrub_mfma_kernel, unaligned rows shorter than 16 bytes: the two
         // passes on this stream.  The correctness path of rare shapes.
-        if ((rc = launch_verify(c, plan, data, data_rs, data_bs, parity, parity_rs, parity_bs, S, nblocks, bad, stream)))
-            return rc;
+        if ((rc = launch_verify(c, plan, rows, bad, stream))) return rc;
         HIP_TRY(hipMemsetAsync(raw, 0, nblocks * n * sizeof(uint32_t), stream));
-        if ((rc = launch_crc(c, data, data_rs, data_bs, uint32_t(k), S, nblocks, raw, n, stream, false))) return rc;
-        return launch_crc(c, parity, parity_rs, parity_bs, uint32_t(m), S, nblocks, raw + k, n, stream, false);
+        if ((rc = launch_crc(c, rows.data, rows.data_rs, rows.data_bs, uint32_t(k), S, nblocks, raw, n, stream, false)))
+            return rc;
+        return launch_crc(c, rows.parity, rows.parity_rs, rows.parity_bs, uint32_t(m), S, nblocks, raw + k, n, stream,
+                          false);
     }
     if ((rc = ensure_crc_tables(c))) return rc;
     const DevTile& tile = plan.tiles[0];
@@ -57,12 +56,11 @@ int launch_scrub(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t da
     for (uint64_t b0 = 0; b0 < nblocks; b0 += max_blocks) {
         const uint64_t nb = std::min(max_blocks, nblocks - b0);
         uint32_t nunits = uint32_t(nb * upb);
-        const uint8_t* inb = data + b0 * data_bs;
-        const uint8_t* parb = parity + b0 * parity_bs;
+        StripeRows r = rows.from(b0, nb);
         uint32_t* badb = bad + b0 * m;
         uint8_t* rb = sc.p + b0 * rec_per_block;
-        void* args[] = {&pd,    &inb,   &parb,  &data_bs, &data_rs, &parity_bs, &parity_rs, &S32,
-                        &cpb32, &tpb32, &upb32, &nunits,  &badb,    &m32,       &ctb,       &rb};
+        void* args[] = {&pd,    &r.data, &r.parity, &r.data_bs, &r.data_rs, &r.parity_bs, &r.parity_rs, &S32,
+                        &cpb32, &tpb32,  &upb32,    &nunits,    &badb,      &m32,         &ctb,         &rb};
         HIP_TRY(hipLaunchKernel(fn, dim3(nunits), dim3(kWG), args, 0, stream));  // a workgroup per unit
     }
     // the records' combine, as behind rs_fused_mfma_kernel (launch_plan_crc): a persistent grid of
@@ -74,10 +72,7 @@ int launch_scrub(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint64_t da
     const uint64_t items = nblocks * ((n + 3) / 4);
     const uint32_t grid = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>((items + 3) / 4, uint64_t(c->num_cu) * 8)));
     HIP_TRY(hipLaunchKernel(crc16_combine_mfma_kernel(), dim3(grid), dim3(kWG), cargs, 0, stream));
-    char buf[96];
-    std::snprintf(buf, sizeof buf, "rs_scrub_mfma_kernel<K=%d,MT=%d>%s", tile.K, tile.MT, ua ? ",UA" : "");
-    set_last_kernel(c, buf);
-    return hip_status(hipGetLastError());
+    return tiles_launched(c, "scrub_mfma", layout, tile);
 }
 
 namespace {
@@ -90,29 +85,11 @@ int scrub_host(rsmi_ctx* c, const uint8_t* data, size_t data_block_stride, const
         return rc;
     if (nblocks == 0) return RSMI_OK;
     const size_t m = size_t(c->m), n = size_t(c->k) + m;
-    const size_t flag_bytes = nblocks * m * sizeof(uint32_t), raw_bytes = nblocks * n * sizeof(uint32_t);
-    uint32_t* d_bad = nullptr;
-    uint32_t* d_raw = nullptr;
+    StripeResults r;
     StripeCheck chk;
-    chk.prepare = [&]() -> int {
-        int rc = reserve(c->d_vbad, c->vbad_cap, flag_bytes + raw_bytes);
-        d_bad = reinterpret_cast<uint32_t*>(c->d_vbad);
-        d_raw = d_bad + nblocks * m;
-        return rc;
-    };
-    chk.launch = [&](const Plan& plan, const uint8_t* d, uint64_t d_rs, uint64_t d_bs, const uint8_t* p, uint64_t p_rs,
-                     uint64_t p_bs, uint64_t nb, uint64_t b0, hipStream_t st) -> int {
-        return launch_scrub(c, plan, d, d_rs, d_bs, p, p_rs, p_bs, S, nb, d_bad + b0 * m, d_raw + b0 * n, st);
-    };
-    chk.fetch = [&](hipStream_t st) -> int {
-        if (st) {
-            HIP_TRY(hipMemcpyAsync(bad_out, d_bad, flag_bytes, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(raw_out, d_raw, raw_bytes, hipMemcpyDeviceToHost, st));
-        } else {
-            HIP_TRY(hipMemcpy(bad_out, d_bad, flag_bytes, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(raw_out, d_raw, raw_bytes, hipMemcpyDeviceToHost));
-        }
-        return RSMI_OK;
+    stripe_results(c, nblocks, n, raw_out, bad_out, r, chk);
+    chk.launch = [&](const Plan& plan, const StripeRows& rows, uint64_t b0, hipStream_t st) -> int {
+        return launch_scrub(c, plan, rows, r.d_bad + b0 * m, r.d_words + b0 * n, st);
     };
     return verify_host_impl(c, data, data_block_stride, parity, parity_block_stride, S, nblocks, chk);
 }
@@ -127,15 +104,11 @@ extern "C" {
 int rsmi_scrub_batch_dev(rsmi_ctx* c, const uint8_t* d_data, size_t data_shard_stride, size_t data_block_stride,
                          const uint8_t* d_parity, size_t parity_shard_stride, size_t parity_block_stride, size_t S,
                          size_t nblocks, uint32_t* d_bad_out, uint32_t* d_raw_out, void* stream) try {
-    int rc = check_stripe_dev_args(c, d_data, data_shard_stride, d_parity, parity_shard_stride, S,
-                                   d_bad_out && d_raw_out ? d_bad_out : nullptr);
-    if (rc) return rc;
-    if (nblocks == 0) return RSMI_OK;
-    std::shared_ptr<Plan> plan;
-    std::unique_lock<std::mutex> lock;
-    if ((rc = begin_stripe_dev_call(c, lock, plan))) return rc;
-    return launch_scrub(c, *plan, d_data, data_shard_stride, data_block_stride, d_parity, parity_shard_stride,
-                        parity_block_stride, S, nblocks, d_bad_out, d_raw_out, static_cast<hipStream_t>(stream));
+    return stripe_dev_call(
+        c, d_data, data_shard_stride, data_block_stride, d_parity, parity_shard_stride, parity_block_stride, S, nblocks,
+        d_bad_out && d_raw_out ? d_bad_out : nullptr, [&](const Plan& plan, const StripeRows& rows) {
+            return launch_scrub(c, plan, rows, d_bad_out, d_raw_out, static_cast<hipStream_t>(stream));
+        });
 } catch (...) {
     return rsmi::impl::exception_status();
 }

@@ -334,7 +334,7 @@ def _body(src, name, ret="int"):
 
 
 def test_predicate_matches_source():
-    """expected_form() is what launch_plan, launch_plan_crc and stripe_layout (launch_verify's
+    """expected_form() is what launch_plan, launch_plan_crc and StripeRows::layout (launch_verify's
     test) say, and the host path rule of leg 4 is what encode_host_impl says: an edit to any of them
     fails here instead of silently retargeting the cases."""
     with open(os.path.join(CSRC, "rsmi_core.cpp")) as f:
@@ -347,11 +347,18 @@ def test_predicate_matches_source():
         host = _body(f.read(), "encode_host_impl")
     with open(os.path.join(CSRC, "rsmi_impl.hpp")) as f:
         impl = f.read()
-    plan_crc, verify = _body(crc_src, "launch_plan_crc"), _body(ver_src, "stripe_layout", "StripeLayout")
+    plan_crc, verify = _body(crc_src, "launch_plan_crc"), _body(ver_src, "StripeRows::layout", "StripeLayout")
     scratch = _body(ver_src, "encode_into_scratch")
     launch = _body(ver_src, "launch_verify")
-    assert "stripe_layout(data, data_rs, data_bs, parity, parity_rs, parity_bs, S)" in launch
-    assert "{&enc, &enc_rs, &enc_bs, &parb, &parity_rs, &parity_bs, &S, &m32, &nb, &badb}" in launch
+    impl1 = " ".join(impl.split())
+    # the rows descriptor: the members in the header's order, and the one place that applies a block stride
+    assert ("const uint8_t* data = nullptr; uint64_t data_rs = 0, data_bs = 0; const uint8_t* parity = nullptr; "
+            "uint64_t parity_rs = 0, parity_bs = 0; uint64_t S = 0, nblocks = 0;") in impl1
+    assert ("StripeRows r = *this; r.data += b0 * data_bs; r.parity += b0 * parity_bs; r.nblocks = nb; return r;"
+            in impl1)
+    assert "const StripeLayout layout = rows.layout();" in launch
+    assert ("{&enc, &enc_rs, &enc_bs, &r.parity, &r.parity_rs, &r.parity_bs, &r.S, &m32, &r.nblocks, &badb}"
+            in launch)
     assert ("const bool aligned = ((reinterpret_cast<uintptr_t>(in) | tba) % 16 == 0) && "
             "((reinterpret_cast<uintptr_t>(out) | tba) % 16 == 0) && in_rs % 16 == 0 && in_bs % 16 == 0 && "
             "out_rs % 16 == 0 && out_bs % 16 == 0 && in_rs >= round_up(S, 16) && out_rs >= round_up(S, 16) && "
@@ -372,12 +379,17 @@ def test_predicate_matches_source():
         assert body.count("const bool aligned =") == 1 and body.count("const bool ua =") == 1
     assert "inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }" in impl
     # the fallback of the verify compares scratch rows at pitch round_up(S, 16) with the stored ones
-    assert "const uint64_t Sp = round_up(S, 16);" in scratch
-    assert "const uint64_t enc_bs = m * Sp, enc_rs = Sp;" in scratch and "fn(b0, nb, vs.p, enc_rs, enc_bs)" in scratch
+    assert "const uint64_t Sp = round_up(rows.S, 16);" in scratch
+    assert "const StripeRows sub = rows.from(b0, std::min(chunk, rows.nblocks - b0));" in scratch
+    assert "fn(b0, sub, vs.p, Sp, m * Sp)" in scratch  # enc, enc_rs, enc_bs
     # the entry points hand the caller's six numbers on unchanged, in the header's order
     tail = ("d_data, data_shard_stride, data_block_stride, d_parity, parity_shard_stride, parity_block_stride, "
             "S, nblocks, ")
-    assert " ".join(ver_src.split()).count("return launch_verify(c, *plan, " + tail + "d_bad_out,") == 1
+    assert " ".join(ver_src.split()).count(
+        "return stripe_dev_call( c, " + tail + "d_bad_out, [&](const Plan& plan, const StripeRows& rows) { "
+        "return launch_verify(c, plan, rows, d_bad_out,") == 1
+    assert impl1.count("return launch(*plan, StripeRows{d_data, data_shard_stride, data_block_stride, d_parity, "
+                       "parity_shard_stride, parity_block_stride, S, nblocks});") == 1
     assert " ".join(crc_src.split()).count("rc = launch_encode_crc(c, *plan, " + tail + "d_raw_out, st);") == 1
     # leg 4: small_path() below
     assert "const size_t total = nblocks * (k + m) * S;" in host

@@ -297,12 +297,12 @@ def test_sheet_is_what_it_is_there_for(k, m):
 
 
 def test_rule_matches_source():
-    """expected_form() is what stripe_layout says for the arguments launch_mixed gives it, and
+    """expected_form() is what StripeRows::layout says for the rows launch_mixed gives it, and
     expected_label() relies on what launch_mixed does: per segment of 2^22 blocks, the classes in
     ascending MT, behind them the fallback's runs in block order; a class for the K of
     fill_mixed_k and one-tile plans only."""
     with open(os.path.join(CSRC, "rsmi_verify.cpp")) as f:
-        layout = _body(f.read(), "stripe_layout", "StripeLayout")
+        layout = _body(f.read(), "StripeRows::layout", "StripeLayout")
     with open(MIXED_CPP) as f:
         mixed = _body(f.read(), "launch_mixed")
     with open(os.path.join(CSRC, "rs_mixed_kernels.hip")) as f:
@@ -317,7 +317,9 @@ def test_rule_matches_source():
             in layout)
     assert "return aligned ? StripeLayout::kAligned : ua ? StripeLayout::kUA : StripeLayout::kNeither;" in layout
     assert "inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }" in impl
-    assert "const StripeLayout layout = stripe_layout(base, rs, bs, base, rs, bs, S);" in mixed
+    assert "const StripeLayout layout = StripeRows{base, rs, bs, base, rs, bs, S, nb}.layout();" in mixed
+    assert ("const uint8_t* data = nullptr; uint64_t data_rs = 0, data_bs = 0; const uint8_t* parity = nullptr; "
+            "uint64_t parity_rs = 0, parity_bs = 0; uint64_t S = 0, nblocks = 0;") in " ".join(impl.split())
     assert "const bool aligned = layout == StripeLayout::kAligned;" in mixed
     assert ("const bool fast = layout != StripeLayout::kNeither && pl.tiles.size() == 1 && t.K == K && K <= 16 && "
             "(aligned ? mixed_kernels().fn : mixed_kernels().ua)[K][t.MT] != nullptr;") in mixed

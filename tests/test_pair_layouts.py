@@ -407,33 +407,44 @@ def test_label_rule_matches_source():
         with open(os.path.join(CSRC, name)) as f:
             src[name] = " ".join(f.read().split())
     pair, heal, scrub = src["rsmi_pair.cpp"], src["rsmi_heal_pair.cpp"], src["rsmi_scrub.cpp"]
-    halves = "data, data_rs, data_bs, parity, parity_rs, parity_bs, S, nblocks, "
-    assert "rc = launch_locate(c, plan, " + halves + "culprit, bad, stream, &fused);" in pair
+    assert "if ((rc = launch_locate(c, plan, rows, culprit, bad, stream, &fused))) return rc;" in pair
     assert ("if (c->m <= 2) { if ((rc = launch_pair_verdict(culprit, nullptr, n32, 0, nblocks, out, stream))) "
             "return rc; return hip_status(hipGetLastError()); }") in pair
     assert "if (fused != StripeLayout::kNeither) {" in pair
-    assert "void* fn = (aligned ? pair_kernels().fn : pair_kernels().ua)[t.K][t.MT];" in pair
-    assert '"rs_locate_pair_kernel<K=%d,MT=%d>%s", t.K, t.MT, aligned ? "" : ",UA"' in pair
+    # stripe_kernel and tiles_launched (rsmi_verify.cpp; tests/test_stripe_layouts.py pins them):
+    # null for kNeither or K > 16, else the layout's table entry; "rs_<name>_kernel<K=..,MT=..>[,UA]"
+    assert "void* fn = stripe_kernel(pair_kernels(), fused, t);" in pair
+    assert 'return tiles_launched(c, "locate_pair", fused, t);' in pair
     assert 'set_last_kernel(c, "rs_locate_pair_rows_kernel");' in pair
-    assert "int rc = launch_locate_pair(c, plan, " + halves + "out, bad, stream, &pl);" in heal
+    assert "int rc = launch_locate_pair(c, plan, rows, out, bad, stream, &pl);" in heal
     assert "if (c->m == 1) return RSMI_OK;" in heal
-    assert "if (c->m == 2) return launch_heal_named(c, plan, pl.fused, " + halves + "pl.culprit, stream);" in heal
+    assert "if (c->m == 2) return launch_heal_named(c, plan, pl.fused, rows, pl.culprit, stream);" in heal
     assert "if (pl.fused != StripeLayout::kNeither) {" in heal
-    assert "void* fn = (aligned ? heal_pair_kernels().fn : heal_pair_kernels().ua)[t.K][t.MT];" in heal
-    assert '"rs_heal_pair_kernel<K=%d,MT=%d>%s", t.K, t.MT, aligned ? "" : ",UA"' in heal
-    assert 'set_last_kernel(c, "rs_heal_pair_rows_kernel");' in heal
-    assert ("const StripeLayout layout = stripe_layout(data, data_rs, data_bs, parity, parity_rs, parity_bs, S);"
+    assert "void* fn = stripe_kernel(heal_pair_kernels(), pl.fused, t);" in heal
+    assert 'return tiles_launched(c, "heal_pair", pl.fused, t);' in heal
+    assert ('return launch_heal_rows(c, plan, heal_pair_rows_kernel(), "rs_heal_pair_rows_kernel", rows, out, 2, '
+            "stream);") in heal
+    assert "const StripeLayout layout = rows.layout();" in scrub
+    assert ("void* fn = plan.tiles.size() == 1 ? stripe_kernel(scrub_kernels(), layout, plan.tiles[0]) : nullptr;"
             in scrub)
-    assert ("if (plan.tiles.size() == 1 && plan.tiles[0].K <= 16 && (aligned || ua)) fn = (aligned ? "
-            "scrub_kernels().fn : scrub_kernels().ua)[plan.tiles[0].K][plan.tiles[0].MT];") in scrub
     assert "if (!fn) {" in scrub
-    assert '"rs_scrub_mfma_kernel<K=%d,MT=%d>%s", tile.K, tile.MT, ua ? ",UA" : ""' in scrub
-    # the entry points hand the caller's six numbers on unchanged, in the header's order
+    assert 'return tiles_launched(c, "scrub_mfma", layout, tile);' in scrub
+    # the entry points hand the caller's six numbers on unchanged, in the header's order, and
+    # stripe_dev_call builds the rows from them in that order
     tail = ("d_data, data_shard_stride, data_block_stride, d_parity, parity_shard_stride, parity_block_stride, S, "
             "nblocks, ")
-    assert pair.count("return launch_locate_pair(c, *plan, " + tail + "d_pair_out, d_bad_out,") == 1
-    assert heal.count("return launch_heal_pair(c, *plan, " + tail + "d_pair_out, d_bad_out,") == 1
-    assert scrub.count("return launch_scrub(c, *plan, " + tail + "d_bad_out, d_raw_out,") == 1
+    with open(os.path.join(CSRC, "rsmi_impl.hpp")) as f:
+        impl = " ".join(f.read().split())
+    assert impl.count("return launch(*plan, StripeRows{d_data, data_shard_stride, data_block_stride, d_parity, "
+                      "parity_shard_stride, parity_block_stride, S, nblocks});") == 1
+    assert ("const uint8_t* data = nullptr; uint64_t data_rs = 0, data_bs = 0; const uint8_t* parity = nullptr; "
+            "uint64_t parity_rs = 0, parity_bs = 0; uint64_t S = 0, nblocks = 0;") in impl
+    for text, out, call in ((pair, "d_pair_out", "launch_locate_pair(c, plan, rows, d_pair_out, d_bad_out,"),
+                            (heal, "d_pair_out", "launch_heal_pair(c, plan, rows, d_pair_out, d_bad_out,"),
+                            (scrub, "d_bad_out && d_raw_out ? d_bad_out : nullptr",
+                             "launch_scrub(c, plan, rows, d_bad_out, d_raw_out,")):
+        assert text.count("return stripe_dev_call( c, " + tail + out +
+                          ", [&](const Plan& plan, const StripeRows& rows) { return " + call) == 1, call
     for name, fill, mts in (("rs_pair_kernels.hip", "fill_pair", [3, 4]),
                             ("rs_heal_pair_kernels.hip", "fill_heal_pair", [3, 4]),
                             ("rs_scrub_kernels.hip", "fill_scrub", [1, 2, 3, 4])):

@@ -217,15 +217,25 @@ def test_label_rule_matches_source():
         with open(os.path.join(CSRC, name)) as f:
             src[name] = " ".join(f.read().split())
     ver, loc, heal = src["rsmi_verify.cpp"], src["rsmi_locate.cpp"], src["rsmi_heal.cpp"]
-    assert "if (t.K > 16 || !(aligned ? verify_kernels().fn : verify_kernels().ua)[t.K][t.MT]) fast = false;" in ver
-    assert "if (loc && plan.tiles.size() == 1) lfn = (aligned ? locate_kernels().fn : locate_kernels().ua)" in ver
-    assert 'lfn ? "locate" : "verify", t.K, t.MT, ua ? ",UA" : ""' in ver
+    # the table lookup and the label every tile launch shares
+    assert ("void* stripe_kernel(const StripeKernelTable& table, StripeLayout layout, const DevTile& t) { "
+            "if (layout == StripeLayout::kNeither || t.K > 16) return nullptr; "
+            "return (layout == StripeLayout::kAligned ? table.fn : table.ua)[t.K][t.MT]; }") in ver
+    assert ('"rs_%s_kernel<K=%d,MT=%d>%s", name, t.K, t.MT, layout == StripeLayout::kUA ? ",UA" : ""); '
+            "set_last_kernel(c, buf);") in ver
+    assert "if (!stripe_kernel(verify_kernels(), layout, t)) fast = false;" in ver
+    assert ("void* lfn = loc && plan.tiles.size() == 1 ? stripe_kernel(locate_kernels(), layout, plan.tiles[0]) : "
+            "nullptr;") in ver
+    assert 'return tiles_launched(c, lfn ? "locate" : "verify", layout, plan.tiles.back());' in ver
     assert 'set_last_kernel(c, "rs_compare_rows_kernel");' in ver
     assert "if (m == 1) {" in loc and "if (plan.tiles.size() == 1) {" in loc
     assert 'if (loc.fused == StripeLayout::kNeither) {' in loc and 'set_last_kernel(c, "rs_locate_rows_kernel");' in loc
     assert "if (c->m == 1) return RSMI_OK;" in heal and "if (fused != StripeLayout::kNeither) {" in heal
-    assert '"rs_heal_kernel<K=%d,MT=%d>%s", t.K, t.MT, aligned ? "" : ",UA"' in heal
-    assert 'set_last_kernel(c, "rs_heal_rows_kernel");' in heal
+    assert "void* fn = stripe_kernel(heal_kernels(), fused, t);" in heal
+    assert 'return tiles_launched(c, "heal", fused, t);' in heal
+    assert ('return launch_heal_rows(c, plan, heal_rows_kernel(), "rs_heal_rows_kernel", rows, culprit, 1, stream);'
+            in heal)
+    assert "set_last_kernel(c, label);" in heal
 
 
 def _at(side, b, r):
