@@ -353,6 +353,7 @@ rsmi_ctx* lane_context(rsmi_ctx* c, int lane, int* rc) {
         x->opt_crc32_fold = c->opt_crc32_fold;
         x->opt_fused_fold = c->opt_fused_fold;
         x->opt_waves_per_cu = c->opt_waves_per_cu;
+        x->opt_launch_units_max.store(c->opt_launch_units_max.load());
         x->opt_zero_copy = c->opt_zero_copy;
         x->opt_small_bytes = c->opt_small_bytes;
         x->opt_coalesce_pipeline = c->opt_coalesce_pipeline;
@@ -486,6 +487,15 @@ long rsmi_get_stat(const rsmi_ctx* c, const char* key) {
     if (!std::strcmp(key, "coalesced_batches")) return long(c->coal.batches());
     if (!std::strcmp(key, "coalesced_wakes")) return long(c->coal.wakes());
     if (!std::strcmp(key, "coalesced_wake_ns")) return long(c->coal.wake_ns());
+    // the option's value in force (an atomic, read without ctx->mu like the counters)
+    if (!std::strcmp(key, "launch_units_max")) return c->opt_launch_units_max.load();
+    if (!std::strcmp(key, "split_launches")) {  // the context's and its coalescing lanes'
+        long v = c->split_launches.load(std::memory_order_relaxed);
+        std::lock_guard<std::mutex> g(c->lanes_mu);
+        for (const rsmi_ctx* l : c->lanes)
+            if (l) v += l->split_launches.load(std::memory_order_relaxed);
+        return v;
+    }
     return -1;
 }
 

@@ -256,6 +256,12 @@ int launch_plan(rsmi_ctx* c, const Plan& plan, const uint8_t* in, uint64_t in_rs
         for (const DevTile& t : plan.tiles)
             if (t.K > 16 || !(aligned ? fast_kernels().fn_tb : fast_kernels().ua_tb)[t.K][t.MT] || (!aligned && !ua))
                 return RSMI_ERR_INVALID_ARG;
+    // a table is never cut (its entries are bases, not a range): one launch, or the callers' fallback
+    const uint64_t cpb = (S + 15) / 16;
+    const uint64_t tpb = (cpb + uint64_t(kWave) - 1) / uint64_t(kWave);
+    // split into launches whose tile count stays within option launch_units_max
+    const uint64_t max_blocks = std::max<uint64_t>(1, uint64_t(c->opt_launch_units_max) / tpb);
+    if (tb && nblocks > max_blocks) return RSMI_ERR_INVALID_ARG;
     for (const DevTile& t : plan.tiles) {
         const int NT = auto_cache_policy(t.K, t.MT);
         void* fn = nullptr;
@@ -273,8 +279,6 @@ int launch_plan(rsmi_ctx* c, const Plan& plan, const uint8_t* in, uint64_t in_rs
         }
         if (fuse && !fn) return RSMI_ERR_INVALID_ARG;
         if (fn) {
-            const uint64_t cpb = (S + 15) / 16;
-            const uint64_t tpb = (cpb + uint64_t(kWave) - 1) / uint64_t(kWave);
             constexpr int wpg = kFastWG / kWave;
             // One tile per wave: the hardware dispatcher hands each free slot the next workgroup,
             // which balances the launch across CUs and XCDs of uneven effective bandwidth.  A
@@ -284,8 +288,6 @@ int launch_plan(rsmi_ctx* c, const Plan& plan, const uint8_t* in, uint64_t in_rs
             // strides over the remaining tiles).
             long wg_cap = std::numeric_limits<long>::max();
             if (c->opt_waves_per_cu > 0) wg_cap = std::max(1L, long(c->num_cu) * c->opt_waves_per_cu / wpg);
-            // split into launches whose tile count fits 32 bits
-            const uint64_t max_blocks = std::max<uint64_t>(1, (uint64_t(1) << 31) / tpb);
             for (uint64_t b0 = 0; b0 < nblocks; b0 += max_blocks) {
                 const uint64_t nb = std::min(max_blocks, nblocks - b0);
                 uint32_t ntiles = uint32_t(nb * tpb);
@@ -299,10 +301,11 @@ int launch_plan(rsmi_ctx* c, const Plan& plan, const uint8_t* in, uint64_t in_rs
                 uint32_t* ctail = fuse && fuse->tail ? fuse->tail + b0 * uint64_t(t.K + t.MT) : nullptr;
                 NoBases nob;
                 // a table's completion flag is armed only when this one launch is the whole job
+                // (a table is one launch per tile: nblocks <= max_blocks, checked above)
                 BlockBases tbl_args;
                 if (tb) {
                     tbl_args = *tb;
-                    if (plan.tiles.size() != 1 || nblocks > max_blocks) tbl_args.done_flag = nullptr;
+                    if (plan.tiles.size() != 1) tbl_args.done_flag = nullptr;
                     if (armed) *armed = tbl_args.done_flag != nullptr;
                 }
                 void* bases = tb ? static_cast<void*>(&tbl_args) : static_cast<void*>(&nob);
@@ -314,6 +317,7 @@ int launch_plan(rsmi_ctx* c, const Plan& plan, const uint8_t* in, uint64_t in_rs
                 void* args[] = {&pd,    &inb,   &outb,   &in_bs, &in_rs, &out_bs, &out_rs, &S32,
                                 &cpb32, &tpb32, &ntiles, &head,  &ctbl,  &crec,   &ctail,  bases};
                 HIP_TRY(hipLaunchKernel(fn, dim3(uint32_t(wgs)), dim3(uint32_t(wpg * kWave)), args, 0, stream));
+                c->split_launches.fetch_add(1, std::memory_order_relaxed);
             }
             std::string label = kernel_label(t.K, t.MT, NT, true);
             if (ua) label += ",UA";
@@ -553,6 +557,9 @@ int apply_option(rsmi_ctx* c, const char* key, long value) {
     } else if (!std::strcmp(key, "waves_per_cu")) {
         if (value < 0) return RSMI_ERR_INVALID_ARG;
         c->opt_waves_per_cu = value;
+    } else if (!std::strcmp(key, "launch_units_max")) {
+        if (value < 0 || value > long(kLaunchUnitsDefault)) return RSMI_ERR_INVALID_ARG;
+        c->opt_launch_units_max.store(value ? value : long(kLaunchUnitsDefault));
     } else if (!std::strcmp(key, "inject_host_fault")) {
         if (value < 0 || value > 1000) return RSMI_ERR_INVALID_ARG;
         c->opt_inject_host_fault.store(int(value));

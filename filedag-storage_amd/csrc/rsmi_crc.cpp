@@ -251,6 +251,10 @@ int launch_plan_crc(rsmi_ctx* c, const Plan& plan, const uint8_t* in, size_t in_
         const size_t upb = (tpb + kFusedUnitTiles - 1) / kFusedUnitTiles;
         const size_t nacc = (nsh + 1) / 2;  // two-shard accumulators: a record byte per lane each
         const size_t rec_per_block = upb * nacc * kWave;
+        // launches of at most launch_units_max units (a workgroup each); a table is never cut (its
+        // entries are bases, not a range): one launch, or the callers' fallback
+        const uint64_t max_blocks = std::max<uint64_t>(1, uint64_t(c->opt_launch_units_max) / upb);
+        if (tb && nblocks > max_blocks) return RSMI_ERR_INVALID_ARG;
         CrcScratch& sc = crc_scratch(c, st);
         if ((rc = reserve_on(sc.d_chunks, sc.chunks_cap, nblocks * rec_per_block, st))) return rc;
         uint8_t* rec = sc.d_chunks;
@@ -284,8 +288,6 @@ int launch_plan_crc(rsmi_ctx* c, const Plan& plan, const uint8_t* in, size_t in_
             HIP_TRY(hipMemsetAsync(sc.d_fctr, 0, nblocks * 4, st));
             sc.fctr_cap = nblocks;
         }
-        // launches of at most 2^31 units (32-bit unit index)
-        const uint64_t max_blocks = std::max<uint64_t>(1, (uint64_t(1) << 31) / upb);
         for (uint64_t b0 = 0; b0 < nblocks; b0 += max_blocks) {
             const uint64_t nb = std::min<uint64_t>(max_blocks, nblocks - b0);
             uint32_t nunits = uint32_t(nb * upb);
@@ -296,17 +298,19 @@ int launch_plan_crc(rsmi_ctx* c, const Plan& plan, const uint8_t* in, size_t in_
             uint32_t* rw = raw + b0 * nsh;
             NoBases nob;
             // a table's completion flag is armed only when this one launch is the whole job (the
-            // combine inside): a separate combine launch would still be writing R after it
+            // combine inside): a separate combine launch would still be writing R after it.  A
+            // table is one launch (nblocks <= max_blocks, checked above)
             BlockBases tbl_args;
             if (tb) {
                 tbl_args = *tb;
-                if (!inline_combine || nblocks > max_blocks) tbl_args.done_flag = nullptr;
+                if (!inline_combine) tbl_args.done_flag = nullptr;
                 if (armed) *armed = tbl_args.done_flag != nullptr;
             }
             void* bases = tb ? static_cast<void*>(&tbl_args) : static_cast<void*>(&nob);
             void* args[] = {&pd,    &inb,   &outb,   &ibs, &irs, &obs, &ors, &S32, &cpb32,
                             &tpb32, &upb32, &nunits, &ctb, &rb,  &cb,  &rw,  &sh,  bases};
             HIP_TRY(hipLaunchKernel(fn, dim3(nunits), dim3(kWG), args, 0, st));  // a workgroup per unit
+            c->split_launches.fetch_add(1, std::memory_order_relaxed);
         }
         if (!inline_combine) {
             uint32_t nacc32 = uint32_t(nacc), nsh32 = uint32_t(nsh);

@@ -87,6 +87,20 @@ struct CrcFuse {
     uint32_t* tail = nullptr;
 };
 
+// Default and upper end of option "launch_units_max": the most tiles (launch_plan,
+// launch_stripe_tiles, a segment of launch_mixed) or units (launch_plan_crc, launch_scrub) one
+// launch takes; a longer batch goes in several launches of whole blocks.  A unit launch runs one
+// workgroup of kWG threads per unit, and a launch stays below 2^32 threads: the
+// MI355X runtime takes a larger grid without an error and wraps its thread count at 2^32, so a
+// fused encode or scrub of 2^24 + 3 units coded three of them and returned RSMI_OK, and a Verify of
+// 2^26 + 5 tiles strode over them with two workgroups for 10.6 s.  The tile launches run a
+// workgroup per 4 tiles and stay four times further below.
+constexpr uint64_t kLaunchUnitsDefault = (uint64_t(1) << 24) - 1;
+static_assert(kLaunchUnitsDefault * kWG < (uint64_t(1) << 32), "a unit launch stays below 2^32 threads");
+// A table launch (BlockBases) is one launch: the table holds bases, not a range that could be
+// cut.  A table whose blocks pass the cap (under the default: 64 blocks of rows past 256 MiB)
+// makes the table forms return RSMI_ERR_INVALID_ARG, and their callers launch per block.
+
 }  // namespace impl
 }  // namespace rsmi
 
@@ -181,6 +195,12 @@ struct rsmi_ctx {
     int opt_crc32_fold = RSMI_CRC32_FOLD_DEFAULT;  // CRC-32 rows pass: 0 = nibble tables, 1 = matrix cores
     int opt_fused_fold = 1;     // aligned fused encode + CRC-16: 0 = nibble tables, 1 = matrix cores (fp4)
     long opt_waves_per_cu = 0;  // grid cap (0 = one tile per wave / the CRC passes' defaults)
+    // tiles or units per launch; atomic (the launchers read it through its conversion): rsmi_get_stat
+    // reads it without ctx->mu
+    std::atomic<long> opt_launch_units_max{long(rsmi::impl::kLaunchUnitsDefault)};
+    // kernel launches of the five loops that cut a batch at opt_launch_units_max (rsmi_get_stat
+    // "split_launches", read without ctx->mu)
+    std::atomic<long> split_launches{0};
     int opt_zero_copy = 1;  // results into page-locked host buffers by kernel stores
     long opt_small_bytes = 2L << 20;  // host calls up to this many shard bytes run zero-copy
     uint8_t* h_small = nullptr;       // page-locked staging of small calls (pageable callers)
@@ -234,7 +254,7 @@ struct rsmi_ctx {
     std::atomic<long> opt_coalesce_lanes{RSMI_COALESCE_LANES};
     std::atomic<long> opt_coalesce_carry{RSMI_COALESCE_CARRY};  // batches a lane runs after its own before handing over (group_commit.hpp)
     std::vector<rsmi_ctx*> lanes;
-    std::mutex lanes_mu;
+    mutable std::mutex lanes_mu;
 };
 
 namespace rsmi {
@@ -341,7 +361,7 @@ int launch_verify(rsmi_ctx* c, const Plan& plan, const StripeRows& rows, uint32_
 int launch_scrub(rsmi_ctx* c, const Plan& plan, const StripeRows& rows, uint32_t* bad, uint32_t* raw,
                  hipStream_t stream);
 // One tile's kernel fn of a stripe call's table over the rows' blocks: one tile per wave unless
-// waves_per_cu caps the grid, in launches whose tile count fits 32 bits.  The tile kernels share
+// waves_per_cu caps the grid, in launches of at most launch_units_max tiles.  The tile kernels share
 // rs_verify_kernel's parameters and, behind them, a plan (rplan) and a second per-block output.
 // Each of the two per-block outputs moves on by its own words per block from launch to launch:
 //   bad    bad_wpb = m: Verify's flags; pair_words(n): the pair words of rs_locate_pair_kernel;

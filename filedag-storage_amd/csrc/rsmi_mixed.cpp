@@ -148,8 +148,9 @@ int launch_mixed(rsmi_ctx* c, const MixedBatch& mb, uint8_t* base, uint64_t rs, 
         cls[p] = fast ? t.MT : kFallback;
     }
 
-    // segments whose block indices and whose tile counts per class fit 32 bits
-    const uint64_t seg = std::min<uint64_t>(std::max<uint64_t>(1, (uint64_t(1) << 31) / tpb), uint64_t(1) << 22);
+    // segments of at most 2^22 blocks whose tile counts per class stay within option launch_units_max
+    const uint64_t seg =
+        std::min<uint64_t>(std::max<uint64_t>(1, uint64_t(c->opt_launch_units_max) / tpb), uint64_t(1) << 22);
     std::vector<MixedEntry> list[kMaxMT + 1];
     for (uint64_t s0 = b0; s0 < b0 + nb; s0 += seg) {
         const uint64_t sn = std::min(seg, b0 + nb - s0);
@@ -213,6 +214,7 @@ int launch_mixed(rsmi_ctx* c, const MixedBatch& mb, uint8_t* base, uint64_t rs, 
                 void* args[] = {&dl, &dp, &sbase, &bs64, &rs64, &S32, &cpb32, &tpb32, &ntiles};
                 const uint64_t wgs = std::min<uint64_t>((uint64_t(ntiles) + wpg - 1) / wpg, uint64_t(wg_cap));
                 HIP_TRY(hipLaunchKernel(fn, dim3(uint32_t(wgs)), dim3(uint32_t(wpg * kWave)), args, 0, stream));
+                c->split_launches.fetch_add(1, std::memory_order_relaxed);
                 char buf[96];
                 std::snprintf(buf, sizeof buf, "rs_mixed_kernel<K=%d,MT=%d>%s", K, mt, aligned ? "" : ",UA");
                 set_last_kernel(c, buf);

@@ -51,8 +51,8 @@ int launch_scrub(rsmi_ctx* c, const Plan& plan, const StripeRows& rows, uint32_t
     const RsPlanDev* pd = tile.dev;
     uint32_t S32 = uint32_t(S), cpb32 = uint32_t(cpb), tpb32 = uint32_t(tpb), upb32 = uint32_t(upb), m32 = uint32_t(m);
     const uint32_t* ctb = c->d_crc_tbl;
-    // launches of at most 2^31 units (32-bit unit index)
-    const uint64_t max_blocks = std::max<uint64_t>(1, (uint64_t(1) << 31) / upb);
+    // launches of at most launch_units_max units (a workgroup each)
+    const uint64_t max_blocks = std::max<uint64_t>(1, uint64_t(c->opt_launch_units_max) / upb);
     for (uint64_t b0 = 0; b0 < nblocks; b0 += max_blocks) {
         const uint64_t nb = std::min(max_blocks, nblocks - b0);
         uint32_t nunits = uint32_t(nb * upb);
@@ -62,6 +62,7 @@ int launch_scrub(rsmi_ctx* c, const Plan& plan, const StripeRows& rows, uint32_t
         void* args[] = {&pd,    &r.data, &r.parity, &r.data_bs, &r.data_rs, &r.parity_bs, &r.parity_rs, &S32,
                         &cpb32, &tpb32,  &upb32,    &nunits,    &badb,      &m32,         &ctb,         &rb};
         HIP_TRY(hipLaunchKernel(fn, dim3(nunits), dim3(kWG), args, 0, stream));  // a workgroup per unit
+        c->split_launches.fetch_add(1, std::memory_order_relaxed);
     }
     // the records' combine, as behind rs_fused_mfma_kernel (launch_plan_crc): a persistent grid of
     // up to 8 workgroups per CU, 4 waves each, over (block, 4-row group) items

@@ -40,8 +40,8 @@ int launch_stripe_tiles(rsmi_ctx* c, void* fn, const DevTile& t, const StripeRow
     constexpr int wpg = kFastWG / kWave;
     long wg_cap = std::numeric_limits<long>::max();
     if (c->opt_waves_per_cu > 0) wg_cap = std::max(1L, long(c->num_cu) * c->opt_waves_per_cu / wpg);
-    // split into launches whose tile count fits 32 bits
-    const uint64_t max_blocks = std::max<uint64_t>(1, (uint64_t(1) << 31) / tpb);
+    // split into launches whose tile count stays within option launch_units_max
+    const uint64_t max_blocks = std::max<uint64_t>(1, uint64_t(c->opt_launch_units_max) / tpb);
     for (uint64_t b0 = 0; b0 < nblocks; b0 += max_blocks) {
         const uint64_t nb = std::min(max_blocks, nblocks - b0);
         uint32_t ntiles = uint32_t(nb * tpb);
@@ -55,6 +55,7 @@ int launch_stripe_tiles(rsmi_ctx* c, void* fn, const DevTile& t, const StripeRow
                         &cpb32, &tpb32,  &ntiles,   &badb,      &m32,       &rplan,       &wordsb};
         const uint64_t wgs = std::min<uint64_t>((ntiles + wpg - 1) / wpg, uint64_t(wg_cap));
         HIP_TRY(hipLaunchKernel(fn, dim3(uint32_t(wgs)), dim3(uint32_t(wpg * kWave)), args, 0, stream));
+        c->split_launches.fetch_add(1, std::memory_order_relaxed);
     }
     return RSMI_OK;
 }

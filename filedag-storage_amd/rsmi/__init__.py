@@ -287,6 +287,13 @@ class Codec:
         return bytes(out)
 
     def set_option(self, key: str, value: int) -> None:
+        """rsmi_set_option (include/rsmi.h lists every key).  Among them: waves_per_cu (grid cap),
+        small_call_bytes, zero_copy, the folds crc16_fold / crc16_fused_fold / crc32_fold, the
+        coalesce_* keys, and launch_units_max: the most tiles (or, for the fused encode + CRC-16
+        and scrub, units of 4 tiles) one kernel launch takes, 1 to 2^24 - 1 (the default; 0 restores
+        it); a longer batch runs as several launches of whole blocks.  stat("launch_units_max")
+        reports the value in force and stat("split_launches") counts those launches.  An unknown key
+        or a value out of range raises RsmiError(ErrInvalidArg)."""
         _check(lib().rsmi_set_option(self._h, key.encode(), int(value)))
 
     def warm(self) -> None:
@@ -451,6 +458,8 @@ class Codec:
                                                 ctypes.addressof(_buf(p)), 1 if data_only else 0))
 
     def stat(self, key: str) -> int:
+        """rsmi_get_stat: the coalesced_* counters, launch_units_max, split_launches; -1 for an
+        unknown key."""
         return lib().rsmi_get_stat(self._h, key.encode())
 
     def encode_batch_host_crc_ptr(self, data_ptr: int, data_bs: int, parity_ptr: int, parity_bs: int, S: int,

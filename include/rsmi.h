@@ -540,7 +540,12 @@ int rsmi_reconstruct_coalesced(rsmi_ctx* ctx, uint8_t* shards, size_t S, const u
 
 /* Counters: "coalesced_calls", "coalesced_batches" (both coalesced entry points); diagnostic:
  * "coalesced_wakes", the wake-ups of callers that slept, and "coalesced_wake_ns", the summed time
- * from each wake-up call to the caller running again.  -1 for an unknown key. */
+ * from each wake-up call to the caller running again.  "launch_units_max": the value of that
+ * option in force.  "split_launches": the kernel launches issued so far by the loops that cut a
+ * batch at "launch_units_max" (encode and reconstruct, the fused encode + CRC-16, the stripe
+ * checks' tile launches, scrub's unit launches, the mixed reconstruct's class launches), by this
+ * context and its coalescing lanes; a call that ran in one piece adds one per kernel, a call that
+ * was cut adds one per piece.  -1 for an unknown key. */
 long rsmi_get_stat(const rsmi_ctx* ctx, const char* key);
 
 /* A host task for the calling thread to run while its next codec call's device work is in
@@ -754,7 +759,12 @@ int rsmi_group_reconstruct_rows_batch_host(rsmi_group* group, uint8_t* shards, s
 /* ------------------------------------------------------------------ tuning / introspection */
 
 /* Options: "waves_per_cu" (grid cap; 0 = the default geometry: one tile per wave for the
- * coding kernels, 48/96 waves per CU for the CRC rows passes), "zero_copy" (1 = default: host
+ * coding kernels, 48/96 waves per CU for the CRC rows passes), "launch_units_max" (the most tiles
+ * -- 1 KiB of every row of a block -- or, for the fused encode + CRC-16 and scrub, units of 4 tiles
+ * that one kernel launch takes; a longer batch runs as several launches of whole blocks, a block
+ * never being cut; 1 to 2^24 - 1, which is the default and keeps every launch below 2^32 threads;
+ * 0 = the default; a table launch of a coalesced group that would pass it runs per block),
+ * "zero_copy" (1 = default: host
  * batch calls whose buffers are page-locked (rsmi_host_alloc) run as one kernel that reads and
  * writes them in place over PCIe, at any size; 2 = the same, also reading inputs in place on
  * the pipeline path; 0 = always the copy-engine pipeline), "small_call_bytes" (host calls moving

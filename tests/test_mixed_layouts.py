@@ -326,8 +326,14 @@ def test_rule_matches_source():
     assert "cls[p] = fast ? t.MT : kFallback;" in mixed
     assert [int(x) for x in re.findall(r"fill_mixed_k<(\d+)>\(x\);", kernels)] == KS
     assert re.findall(r"fill_mixed_km<K, (\d)>\(t\);", kernels) == ["1", "2", "3", "4"]
-    assert ("const uint64_t seg = std::min<uint64_t>(std::max<uint64_t>(1, (uint64_t(1) << 31) / tpb), "
+    assert ("const uint64_t seg = std::min<uint64_t>(std::max<uint64_t>(1, uint64_t(c->opt_launch_units_max) / tpb), "
             "uint64_t(1) << 22);") in mixed
+    assert mixed.count("const uint64_t seg =") == 1 and "<< 31" not in mixed
+    # option launch_units_max defaults to 2^24 - 1 tiles: 2^22 blocks is the smaller arm while a
+    # block has at most 3 tiles, as every segment expected_label counts on has
+    assert "constexpr uint64_t kLaunchUnitsDefault = (uint64_t(1) << 24) - 1;" in impl
+    assert "std::atomic<long> opt_launch_units_max{long(rsmi::impl::kLaunchUnitsDefault)};" in impl
+    assert ((1 << 24) - 1) // 3 >= SEAM
     assert SEAM == 1 << 22   # expected_label's segment
     # the order of the launches inside one segment
     seg_loop = mixed.index("for (uint64_t s0 = b0; s0 < b0 + nb; s0 += seg) {")

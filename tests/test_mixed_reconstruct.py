@@ -172,8 +172,12 @@ def test_chunk_rule_matches_source():
     assert PAST_STREAMS == 40 > kept  # leg 12 stays beyond the eviction threshold
     # leg 11: a segment of launch_mixed is at most 2^22 blocks
     assert src.count("uint64_t(1) << 22") == 1 and SEAM == 1 << 22
-    assert ("const uint64_t seg = std::min<uint64_t>(std::max<uint64_t>(1, (uint64_t(1) << 31) / tpb), "
+    assert ("const uint64_t seg = std::min<uint64_t>(std::max<uint64_t>(1, uint64_t(c->opt_launch_units_max) / tpb), "
             "uint64_t(1) << 22);") in " ".join(src.split())
+    assert src.count("const uint64_t seg =") == 1 and "<< 31" not in src
+    # leg 11 runs one tile per block, where the option's default (2^24 - 1 tiles) is the larger arm
+    with open(os.path.join(os.path.dirname(MIXED_CPP), "rsmi_impl.hpp")) as f:
+        assert "constexpr uint64_t kLaunchUnitsDefault = (uint64_t(1) << 24) - 1;" in f.read()
     assert "uint8_t* sbase = base + (s0 - b0) * bs;" in src
     assert "list[cls[p]].push_back(MixedEntry{uint32_t(b), p});" in src
 
