@@ -245,6 +245,16 @@ struct MixedKernelTable {
     void* ua[17][kMaxMT + 1];
 };
 const MixedKernelTable& mixed_kernels();
+// rsmi_reconstruct_mixed_batch_*_verify (rs_mixed_fused_kernels.hip): rs_mixed_fused_kernel per
+// (K, MT), the shapes of rs_mixed_kernel, aligned and unaligned-window layouts (null: the class
+// takes rs_mixed_kernel and the named rows pass), and the kernel that moves a class's combined
+// checksums from (entry, slot) to (block, row)
+struct MixedFusedKernelTable {
+    void* fn[17][kMaxMT + 1];
+    void* ua[17][kMaxMT + 1];
+};
+const MixedFusedKernelTable& mixed_fused_kernels();
+void* mixed_scatter_kernel();
 
 // CRC-16 of shard rows (crc16.hpp): the device table buffer holds P[15][2][256] (the powers
 // A^(2^i), byte-sliced) and N[32][16] (u16); a wave folds kCrcSegTiles 1 KiB tiles of one row

@@ -470,6 +470,9 @@ void rsmi_close(rsmi_ctx* c) {
             if (!c->scrub_scratch.empty()) (void)hipDeviceSynchronize();
             for (auto& e : c->scrub_scratch)
                 if (e.second.p) (void)hipFree(e.second.p);
+            if (!c->mixed_verify_scratch.empty()) (void)hipDeviceSynchronize();
+            for (auto& e : c->mixed_verify_scratch)
+                if (e.second.p) (void)hipFree(e.second.p);
             if (!c->mixed_scratch.empty()) (void)hipDeviceSynchronize();
             for (auto& e : c->mixed_scratch) {
                 if (e.second.d) (void)hipFree(e.second.d);

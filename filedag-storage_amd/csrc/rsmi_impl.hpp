@@ -17,7 +17,7 @@
 // No CPU compute path anywhere: every byte of parity, reconstructed data or CRC and every verify
 // flag comes out of the HIP kernels (rs_kernels.hip, rs_kernels_tb.hip, rs_crc16_kernels.hip, rs_crc32_kernels.hip,
 // rs_verify_kernels.hip, rs_locate_kernels.hip, rs_heal_kernels.hip, rs_mixed_kernels.hip,
-// rs_pair_kernels.hip, rs_heal_pair_kernels.hip, rs_scrub_kernels.hip).  Kernel headers: rs_gf_tile.hpp (the GF(2^8) tile pipeline), rs_verify_tile.hpp
+// rs_mixed_fused_kernels.hip, rs_pair_kernels.hip, rs_heal_pair_kernels.hip, rs_scrub_kernels.hip).  Kernel headers: rs_gf_tile.hpp (the GF(2^8) tile pipeline), rs_verify_tile.hpp
 // (the stripe checks' tile step), rs_crc_rows.hpp (what the CRC-16 and CRC-32 rows passes share).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -186,6 +186,9 @@ struct rsmi_ctx {
         size_t cap = 0, head = 0;
     };
     std::map<hipStream_t, MixedScratch> mixed_scratch;
+    // ... and of its _verify forms: per stream the unit records of rs_mixed_fused_kernel and the
+    // (entry, slot) checksums their combine leaves for the scatter
+    std::map<hipStream_t, VerifyScratch> mixed_verify_scratch;
     rsmi::Crc32Shift crc32_shift{};  // launch_crc32's per-S shift matrix, for crc32_shift_S
     uint64_t crc32_shift_S = ~uint64_t(0);
     CrcScratch own_scratch;  // the fused encode + CRC-16's scratch on the context's own streams
@@ -506,8 +509,14 @@ void classify_mixed(const rsmi_ctx* c, size_t nblocks, const uint8_t* present, c
 // d16 / d32 (device memory, either may be null): block b0's n words of the by-row checksums, zeroed
 // by the caller on the stream; R / R32 of every row the launches rebuild is added there by the named
 // rows pass behind them, its rows array riding in the same upload as the classes' lists.
+// dver (device memory, the _verify forms; excludes d16 / d32): block b0's n words, zeroed by the
+// caller on the stream; R of every row the launches read (a block's k survivors) and rebuild lands
+// there.  Classes with an rs_mixed_fused_kernel get both from that kernel, its records' combine and
+// the scatter (the stream's mixed_verify_scratch holds what lies between them); every other block
+// is rebuilt as without dver and has its k + rows rows named to the named rows pass.
 int launch_mixed(rsmi_ctx* c, const MixedBatch& mb, uint8_t* base, uint64_t rs, uint64_t bs, uint64_t S, uint64_t b0,
-                 uint64_t nb, hipStream_t stream, uint32_t* d16 = nullptr, uint32_t* d32 = nullptr);
+                 uint64_t nb, hipStream_t stream, uint32_t* d16 = nullptr, uint32_t* d32 = nullptr,
+                 uint32_t* dver = nullptr);
 int ensure_crc_tables(rsmi_ctx* c);
 int ensure_crc32_tables(rsmi_ctx* c);
 // R(row) / R32(row) of the rows the plan rebuilt (want && !present), one row per block at

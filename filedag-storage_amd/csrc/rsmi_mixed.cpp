@@ -8,6 +8,9 @@
 // neither aligned nor unaligned-window take the uniform call's launch_plan, one per run of
 // consecutive blocks with equal masks: the correctness path of rare shapes.  The _crcs forms add the
 // named rows pass (rsmi_crc.cpp launch_crc_named) over the rows just rebuilt, behind those launches.
+// The _verify forms return R of every row read and rebuilt: the classes launch rs_mixed_fused_kernel
+// (rs_mixed_fused_kernels.hip) in the place of rs_mixed_kernel, then the records' combine and the
+// scatter to (block, row); the other blocks have their survivors and rebuilt rows named to that pass.
 
 #include "rsmi_impl.hpp"
 
@@ -108,12 +111,66 @@ int mixed_words(rsmi_ctx* c, hipStream_t st, size_t need, uint8_t*& h, uint8_t*&
     return RSMI_OK;
 }
 
+// One class of a segment on the _verify route: rs_mixed_fused_kernel over the class's units, a
+// workgroup each (at most the class's tiles, so within option launch_units_max as the segment is),
+// the records' combine with the class's entries as its blocks, and the scatter of the (entry, slot)
+// checksums to out[blk * n + row].  list, plans: device memory, as rs_mixed_kernel takes them; rec,
+// comb: the class's share of the stream's mixed_verify_scratch.
+struct MixedFusedClass {
+    const MixedEntry* list;
+    const RsPlanDev* const* plans;
+    uint8_t* base;
+    uint64_t bs, rs, S, cpb, tpb, upb;
+    int K, mt;
+    bool aligned;
+    uint64_t entries;
+    const Crc16Shift* sh;
+    uint8_t* rec;
+    uint32_t* comb;
+    uint32_t* out;
+    uint32_t n;
+};
+int launch_mixed_fused(rsmi_ctx* c, const MixedFusedClass& a, hipStream_t stream) {
+    void* fn = (a.aligned ? mixed_fused_kernels().fn : mixed_fused_kernels().ua)[a.K][a.mt];
+    const MixedEntry* dl = a.list;
+    const RsPlanDev* const* dp = a.plans;
+    uint8_t* base = a.base;
+    uint8_t* rec = a.rec;
+    const uint32_t* ctb = c->d_crc_tbl;
+    uint32_t nunits = uint32_t(a.entries * a.upb);
+    uint32_t S32 = uint32_t(a.S), cpb32 = uint32_t(a.cpb), tpb32 = uint32_t(a.tpb), upb32 = uint32_t(a.upb);
+    uint64_t bs64 = a.bs, rs64 = a.rs;
+    void* args[] = {&dl, &dp, &base, &bs64, &rs64, &S32, &cpb32, &tpb32, &upb32, &nunits, &ctb, &rec};
+    HIP_TRY(hipLaunchKernel(fn, dim3(nunits), dim3(kWG), args, 0, stream));  // a workgroup per unit
+    c->split_launches.fetch_add(1, std::memory_order_relaxed);
+    // a persistent grid of up to 8 workgroups per CU over (entry, 4-slot group) items
+    uint32_t nacc32 = uint32_t((a.K + a.mt + 1) / 2), nsh32 = uint32_t(a.K + a.mt), K32 = uint32_t(a.K), n32 = a.n;
+    uint64_t ne64 = a.entries;
+    const uint8_t* crec = a.rec;
+    uint32_t* comb = a.comb;
+    Crc16Shift sh = *a.sh;
+    void* cargs[] = {&ctb, &crec, &upb32, &nacc32, &nsh32, &sh, &ne64, &comb};
+    const uint64_t items = a.entries * ((uint64_t(nsh32) + 3) / 4);
+    const uint32_t grid = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>((items + 3) / 4, uint64_t(c->num_cu) * 8)));
+    HIP_TRY(hipLaunchKernel(crc16_combine_mfma_kernel(), dim3(grid), dim3(kWG), cargs, 0, stream));
+    uint32_t nitems = uint32_t(a.entries * nsh32);
+    const uint32_t* ccomb = a.comb;
+    uint32_t* out = a.out;
+    void* sargs[] = {&dl, &dp, &ccomb, &nsh32, &K32, &n32, &nitems, &out};
+    HIP_TRY(hipLaunchKernel(mixed_scatter_kernel(), dim3((nitems + kWG - 1) / kWG), dim3(kWG), sargs, 0, stream));
+    char buf[96];
+    std::snprintf(buf, sizeof buf, "rs_mixed_fused_kernel<K=%d,MT=%d>%s", a.K, a.mt, a.aligned ? "" : ",UA");
+    set_last_kernel(c, buf);
+    return RSMI_OK;
+}
+
 }  // namespace
 
 int launch_mixed(rsmi_ctx* c, const MixedBatch& mb, uint8_t* base, uint64_t rs, uint64_t bs, uint64_t S, uint64_t b0,
-                 uint64_t nb, hipStream_t stream, uint32_t* d16, uint32_t* d32) {
+                 uint64_t nb, hipStream_t stream, uint32_t* d16, uint32_t* d32, uint32_t* dver) {
     if (nb == 0 || S == 0) return RSMI_OK;
     const bool crcs = d16 || d32;
+    if (crcs && dver) return RSMI_ERR_INVALID_ARG;
     const size_t n = size_t(c->n), npat = mb.keys.size();
     // launch_plan's layout test, the rows being read and written in place
     const StripeLayout layout = StripeRows{base, rs, bs, base, rs, bs, S, nb}.layout();
@@ -127,6 +184,9 @@ int launch_mixed(rsmi_ctx* c, const MixedBatch& mb, uint8_t* base, uint64_t rs, 
     // per pattern that has a block here: its plan and its class
     std::vector<std::shared_ptr<Plan>> plans(npat);
     std::vector<int> cls(npat, kNoLaunch);
+    // dver: the pattern's class has an rs_mixed_fused_kernel, which also checksums what it reads
+    // and writes; every other pattern with a launch has its rows named to the named rows pass
+    std::vector<uint8_t> fused(npat, 0);
     std::vector<uint8_t> seen(npat, 0);
     std::vector<uint8_t> have(n), want(n);
     const int K = c->k;  // every reconstruct plan reads k survivors
@@ -146,34 +206,57 @@ int launch_mixed(rsmi_ctx* c, const MixedBatch& mb, uint8_t* base, uint64_t rs, 
         const bool fast = layout != StripeLayout::kNeither && pl.tiles.size() == 1 && t.K == K && K <= 16 &&
                           (aligned ? mixed_kernels().fn : mixed_kernels().ua)[K][t.MT] != nullptr;
         cls[p] = fast ? t.MT : kFallback;
+        fused[p] = dver && fast && (aligned ? mixed_fused_kernels().fn : mixed_fused_kernels().ua)[K][t.MT] != nullptr;
+    }
+    const bool any_fused = std::find(fused.begin(), fused.end(), uint8_t(1)) != fused.end();
+    if (any_fused)
+        if (int rc = ensure_crc_tables(c)) return rc;
+    // the fused classes' units: 4 tiles of one block each.  A^e moves a row's value from the end of
+    // its last unit to the row's end (launch_scrub's shift: S and upb alone decide it)
+    const uint64_t upb = (tpb + kFusedUnitTiles - 1) / kFusedUnitTiles;
+    Crc16Shift sh{};
+    if (any_fused) {
+        const int64_t unit_bytes = int64_t(kFusedUnitTiles) * kWave * 16;
+        const uint64_t e =
+            uint64_t(((int64_t(S) - int64_t(upb) * unit_bytes) % int64_t(kCrcOrder) + kCrcOrder) % kCrcOrder);
+        for (int b = 0; b < 16; b++) sh.col[b] = crc16_tables().shift(uint16_t(1u << b), e);
     }
 
     // segments of at most 2^22 blocks whose tile counts per class stay within option launch_units_max
     const uint64_t seg =
         std::min<uint64_t>(std::max<uint64_t>(1, uint64_t(c->opt_launch_units_max) / tpb), uint64_t(1) << 22);
-    std::vector<MixedEntry> list[kMaxMT + 1];
+    // a class's units are at most its tiles, so a segment's fused launches stay within the option too
+    std::vector<MixedEntry> list[kMaxMT + 1], flist[kMaxMT + 1];
     for (uint64_t s0 = b0; s0 < b0 + nb; s0 += seg) {
         const uint64_t sn = std::min(seg, b0 + nb - s0);
         uint8_t* sbase = base + (s0 - b0) * bs;
         for (auto& l : list) l.clear();
+        for (auto& l : flist) l.clear();
         size_t nfast = 0;
         for (uint64_t b = 0; b < sn; b++) {
             const uint32_t p = mb.pat[s0 + b];
             if (cls[p] > 0) {
-                list[cls[p]].push_back(MixedEntry{uint32_t(b), p});
+                if (fused[p])
+                    flist[cls[p]].push_back(MixedEntry{uint32_t(b), p});
+                else
+                    list[cls[p]].push_back(MixedEntry{uint32_t(b), p});
                 nfast++;
             }
         }
         // with checksums: the rows every block of the segment rebuilds, as the named rows pass reads
-        // them (slots = the most rows a block rebuilds, unused slots -1), behind the lists
+        // them (slots = the most rows a block rebuilds, unused slots -1), behind the lists; dver:
+        // ahead of them the k survivors, and only of the blocks no fused kernel takes
+        auto named = [&](uint32_t p) { return cls[p] != kNoLaunch && (crcs || (dver && !fused[p])); };
         uint32_t slots = 0;
-        if (crcs)
+        if (crcs || dver)
             for (uint64_t b = 0; b < sn; b++)
-                if (cls[mb.pat[s0 + b]] != kNoLaunch) slots = std::max<uint32_t>(slots, mb.key_rows[mb.pat[s0 + b]]);
+                if (named(mb.pat[s0 + b]))
+                    slots = std::max<uint32_t>(slots, (dver ? uint32_t(K) : 0u) + mb.key_rows[mb.pat[s0 + b]]);
         const size_t rows_bytes = size_t(sn) * slots * sizeof(int32_t);
         const int32_t* d_rows = nullptr;
         if (nfast || slots) {
             // one upload: the patterns' plan pointers, then the classes' lists in ascending MT
+            // (rs_mixed_kernel's, then rs_mixed_fused_kernel's)
             const size_t ptr_bytes = round_up(npat * sizeof(const RsPlanDev*), 16);
             const size_t list_bytes = round_up(nfast * sizeof(MixedEntry), 16);
             uint8_t *h = nullptr, *d = nullptr;
@@ -182,11 +265,16 @@ int launch_mixed(rsmi_ctx* c, const MixedBatch& mb, uint8_t* base, uint64_t rs, 
             auto* hp = reinterpret_cast<const RsPlanDev**>(h);
             for (size_t p = 0; p < npat; p++) hp[p] = cls[p] > 0 ? plans[p]->tiles[0].dev : nullptr;
             size_t off = ptr_bytes;
-            size_t list_off[kMaxMT + 1] = {};
+            size_t list_off[kMaxMT + 1] = {}, flist_off[kMaxMT + 1] = {};
             for (int mt = 1; mt <= kMaxMT; mt++) {
                 list_off[mt] = off;
                 if (!list[mt].empty()) std::memcpy(h + off, list[mt].data(), list[mt].size() * sizeof(MixedEntry));
                 off += list[mt].size() * sizeof(MixedEntry);
+            }
+            for (int mt = 1; mt <= kMaxMT; mt++) {
+                flist_off[mt] = off;
+                if (!flist[mt].empty()) std::memcpy(h + off, flist[mt].data(), flist[mt].size() * sizeof(MixedEntry));
+                off += flist[mt].size() * sizeof(MixedEntry);
             }
             if (slots) {
                 off = ptr_bytes + list_bytes;
@@ -194,9 +282,13 @@ int launch_mixed(rsmi_ctx* c, const MixedBatch& mb, uint8_t* base, uint64_t rs, 
                 for (uint64_t b = 0; b < sn; b++) {
                     const uint32_t p = mb.pat[s0 + b];
                     uint32_t s = 0;
-                    if (cls[p] != kNoLaunch)
+                    if (named(p)) {
+                        // dver: the first k present rows, the rows every reconstruct plan reads
+                        for (size_t i = 0; dver && i < n && s < uint32_t(K); i++)
+                            if (mb.keys[p][i] == '1') hr[b * slots + s++] = int32_t(i);
                         for (size_t i = 0; i < n; i++)
                             if (mb.keys[p][i] == '2') hr[b * slots + s++] = int32_t(i);
+                    }
                     while (s < slots) hr[b * slots + s++] = -1;
                 }
                 d_rows = reinterpret_cast<const int32_t*>(d + off);
@@ -219,6 +311,32 @@ int launch_mixed(rsmi_ctx* c, const MixedBatch& mb, uint8_t* base, uint64_t rs, 
                 std::snprintf(buf, sizeof buf, "rs_mixed_kernel<K=%d,MT=%d>%s", K, mt, aligned ? "" : ",UA");
                 set_last_kernel(c, buf);
             }
+            // the fused classes: per class the tile kernel over its units, a workgroup each, the
+            // records' combine with the class's entries as its blocks, and the scatter to the rows
+            size_t rec_bytes = 0, comb_words = 0;
+            for (int mt = 1; mt <= kMaxMT; mt++) {
+                rec_bytes += flist[mt].size() * upb * size_t((K + mt + 1) / 2) * kWave;
+                comb_words += flist[mt].size() * size_t(K + mt);
+            }
+            if (rec_bytes) {
+                rsmi_ctx::VerifyScratch& sc = stream_scratch(c->mixed_verify_scratch, stream);
+                rec_bytes = round_up(rec_bytes, 16);
+                if ((rc = reserve_on(sc.p, sc.cap, rec_bytes + comb_words * sizeof(uint32_t), stream))) return rc;
+                uint8_t* rec = sc.p;
+                uint32_t* comb = reinterpret_cast<uint32_t*>(sc.p + rec_bytes);
+                const RsPlanDev* const* dp = reinterpret_cast<const RsPlanDev* const*>(d);
+                uint32_t* vout = dver + (s0 - b0) * n;
+                for (int mt = 1; mt <= kMaxMT; mt++) {
+                    const uint64_t ne = flist[mt].size();
+                    if (!ne) continue;
+                    const MixedFusedClass fc{reinterpret_cast<const MixedEntry*>(d + flist_off[mt]), dp, sbase, bs, rs, S,
+                                             cpb, tpb, upb, K, mt, aligned, ne, &sh, rec, comb, vout, uint32_t(n)};
+                    if ((rc = launch_mixed_fused(c, fc, stream))) return rc;
+                    const uint32_t nacc32 = uint32_t((K + mt + 1) / 2), nitems = uint32_t(ne * uint64_t(K + mt));
+                    rec += ne * upb * nacc32 * kWave;
+                    comb += nitems;
+                }
+            }
         }
         // the fallback: the uniform call's launch per run of consecutive blocks with equal masks
         for (uint64_t b = 0; b < sn;) {
@@ -236,7 +354,8 @@ int launch_mixed(rsmi_ctx* c, const MixedBatch& mb, uint8_t* base, uint64_t rs, 
         if (slots) {
             const NamedRowsArgs a{d_rows, sbase, bs, rs, sbase + uint64_t(K) * rs, bs, rs,
                                   uint32_t(K), uint32_t(n), slots, uint32_t(n)};
-            int rc = launch_crc_named(c, a, S, sn, d16 ? d16 + (s0 - b0) * n : nullptr,
+            uint32_t* o16 = dver ? dver : d16;
+            int rc = launch_crc_named(c, a, S, sn, o16 ? o16 + (s0 - b0) * n : nullptr,
                                       d32 ? d32 + (s0 - b0) * n : nullptr, stream, false);
             if (rc) return rc;
         }
@@ -258,10 +377,12 @@ void write_status(const MixedBatch& mb, size_t nblocks, int32_t* status_out) {
 // null) receive R / R32 of every row the call rebuilt and 0 elsewhere: the named rows pass runs where
 // the rows were rebuilt (in place, over the staging, over the chunk's device rows on its slot's
 // stream before the slot is reused), into ctx->d_crc / d_crc32, read back once at the end.
+// rawv (the _verify form, in place of raw16 / raw32): R of every row the call read or rebuilt, by
+// the same route (launch_mixed's dver), ctx->d_crc being its device side.
 int mixed_host_impl(rsmi_ctx* c, uint8_t* shards, size_t block_stride, size_t S, size_t nblocks,
                     const uint8_t* present, const uint8_t* required, int data_only, int32_t* status_out,
-                    bool crcs = false, uint32_t* raw16 = nullptr, uint32_t* raw32 = nullptr) {
-    if (!c || !shards || !present || (crcs && !raw16 && !raw32)) return RSMI_ERR_INVALID_ARG;
+                    bool crcs = false, uint32_t* raw16 = nullptr, uint32_t* raw32 = nullptr, uint32_t* rawv = nullptr) {
+    if (!c || !shards || !present || (crcs && !raw16 && !raw32 && !rawv)) return RSMI_ERR_INVALID_ARG;
     if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
     if (block_stride < size_t(c->n) * S) return RSMI_ERR_INVALID_ARG;
     if (nblocks == 0) return RSMI_OK;
@@ -272,6 +393,7 @@ int mixed_host_impl(rsmi_ctx* c, uint8_t* shards, size_t block_stride, size_t S,
     if (raw16) std::memset(raw16, 0, raw_sz);
     if (raw32) std::memset(raw32, 0, raw_sz);
     if (!mb.work) {
+        if (rawv) std::memset(rawv, 0, raw_sz);  // with work every word comes back from the device
         write_status(mb, nblocks, status_out);
         return RSMI_OK;
     }
@@ -280,10 +402,11 @@ int mixed_host_impl(rsmi_ctx* c, uint8_t* shards, size_t block_stride, size_t S,
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = size_t(c->n), blk = n * S;
-    if (raw16 && (rc = reserve(c->d_crc, c->crc_cap, raw_sz))) return rc;
+    if ((raw16 || rawv) && (rc = reserve(c->d_crc, c->crc_cap, raw_sz))) return rc;
     if (raw32 && (rc = reserve(c->d_crc32, c->crc32_cap, raw_sz))) return rc;
     uint32_t* d16 = raw16 ? reinterpret_cast<uint32_t*>(c->d_crc) : nullptr;
     uint32_t* d32 = raw32 ? reinterpret_cast<uint32_t*>(c->d_crc32) : nullptr;
+    uint32_t* dv = rawv ? reinterpret_cast<uint32_t*>(c->d_crc) : nullptr;
     // the rows of block b the call moves: in, the present rows; out, the rows it rebuilt
     auto each_row = [&](size_t b, char which, auto&& fn) {
         const uint32_t p = mb.pat[b];
@@ -307,10 +430,12 @@ int mixed_host_impl(rsmi_ctx* c, uint8_t* shards, size_t block_stride, size_t S,
         }
         if (d16) HIP_TRY(hipMemsetAsync(d16, 0, raw_sz, st));
         if (d32) HIP_TRY(hipMemsetAsync(d32, 0, raw_sz, st));
-        if ((rc = launch_mixed(c, mb, dev, S, dbs, S, 0, nblocks, st, d16, d32))) return rc;
+        if (dv) HIP_TRY(hipMemsetAsync(dv, 0, raw_sz, st));
+        if ((rc = launch_mixed(c, mb, dev, S, dbs, S, 0, nblocks, st, d16, d32, dv))) return rc;
         const uint32_t *h16, *h32;
-        if ((rc = readback(c, d16, d32, raw_sz, st, h16, h32))) return rc;
+        if ((rc = readback(c, dv ? dv : d16, d32, raw_sz, st, h16, h32))) return rc;
         HIP_TRY(hipStreamSynchronize(st));
+        if (rawv) std::memcpy(rawv, h16, raw_sz);
         if (raw16) std::memcpy(raw16, h16, raw_sz);
         if (raw32) std::memcpy(raw32, h32, raw_sz);
         if (hs)
@@ -337,8 +462,9 @@ int mixed_host_impl(rsmi_ctx* c, uint8_t* shards, size_t block_stride, size_t S,
                 HIP_TRY(hipMemcpyAsync(st.d_lin + b * blk, h + b * block_stride, blk, hipMemcpyHostToDevice, st.stream));
         if (d16) HIP_TRY(hipMemsetAsync(d16 + b0 * n, 0, nb * n * 4, st.stream));
         if (d32) HIP_TRY(hipMemsetAsync(d32 + b0 * n, 0, nb * n * 4, st.stream));
+        if (dv) HIP_TRY(hipMemsetAsync(dv + b0 * n, 0, nb * n * 4, st.stream));
         if ((rc = launch_mixed(c, mb, st.d_lin, S, blk, S, b0, nb, st.stream, d16 ? d16 + b0 * n : nullptr,
-                               d32 ? d32 + b0 * n : nullptr)))
+                               d32 ? d32 + b0 * n : nullptr, dv ? dv + b0 * n : nullptr)))
             return rc;
         for (size_t b = 0; b < nb; b++) {
             hipError_t e = hipSuccess;
@@ -353,6 +479,7 @@ int mixed_host_impl(rsmi_ctx* c, uint8_t* shards, size_t block_stride, size_t S,
     for (int s = 0; s < ns; s++) HIP_TRY(hipStreamSynchronize(c->staging[s].stream));
     if (raw16) HIP_TRY(hipMemcpy(raw16, d16, raw_sz, hipMemcpyDeviceToHost));
     if (raw32) HIP_TRY(hipMemcpy(raw32, d32, raw_sz, hipMemcpyDeviceToHost));
+    if (rawv) HIP_TRY(hipMemcpy(rawv, dv, raw_sz, hipMemcpyDeviceToHost));
     write_status(mb, nblocks, status_out);
     return RSMI_OK;
 }
@@ -385,11 +512,12 @@ int rsmi_reconstruct_mixed_classify(const rsmi_ctx* c, size_t nblocks, const uin
 namespace {
 
 // rsmi_reconstruct_mixed_batch_dev, and with crcs its _crcs form: d16 / d32 (device memory, not
-// both null) are zeroed on the stream, so that form needs the device even with nothing to rebuild
+// both null) are zeroed on the stream, so that form needs the device even with nothing to rebuild;
+// dver in their place: the _verify form, the same in every other respect
 int mixed_dev_impl(rsmi_ctx* c, uint8_t* d_shards, size_t shard_stride, size_t block_stride, size_t S, size_t nblocks,
                    const uint8_t* present, const uint8_t* required, int data_only, int32_t* status_out, bool crcs,
-                   uint32_t* d16, uint32_t* d32, void* stream) {
-    if (!c || !d_shards || !present || (crcs && !d16 && !d32)) return RSMI_ERR_INVALID_ARG;
+                   uint32_t* d16, uint32_t* d32, void* stream, uint32_t* dver = nullptr) {
+    if (!c || !d_shards || !present || (crcs && !d16 && !d32 && !dver)) return RSMI_ERR_INVALID_ARG;
     if (S == 0) return RSMI_ERR_SHARD_NO_DATA;
     if (shard_stride < S) return RSMI_ERR_INVALID_ARG;
     if (nblocks == 0) return RSMI_OK;
@@ -405,7 +533,9 @@ int mixed_dev_impl(rsmi_ctx* c, uint8_t* d_shards, size_t shard_stride, size_t b
         const size_t raw_sz = nblocks * size_t(c->n) * 4;
         if (d16) HIP_TRY(hipMemsetAsync(d16, 0, raw_sz, st));
         if (d32) HIP_TRY(hipMemsetAsync(d32, 0, raw_sz, st));
-        if (mb.work && (rc = launch_mixed(c, mb, d_shards, shard_stride, block_stride, S, 0, nblocks, st, d16, d32)))
+        if (dver) HIP_TRY(hipMemsetAsync(dver, 0, raw_sz, st));
+        if (mb.work &&
+            (rc = launch_mixed(c, mb, d_shards, shard_stride, block_stride, S, 0, nblocks, st, d16, d32, dver)))
             return rc;
     }
     write_status(mb, nblocks, status_out);
@@ -429,6 +559,25 @@ int rsmi_reconstruct_mixed_batch_dev_crcs(rsmi_ctx* c, uint8_t* d_shards, size_t
                                           uint32_t* d_raw32_out, void* stream) try {
     return mixed_dev_impl(c, d_shards, shard_stride, block_stride, S, nblocks, present, required, data_only, status_out,
                           true, d_raw16_out, d_raw32_out, stream);
+} catch (...) {
+    return rsmi::impl::exception_status();
+}
+
+int rsmi_reconstruct_mixed_batch_dev_verify(rsmi_ctx* c, uint8_t* d_shards, size_t shard_stride, size_t block_stride,
+                                            size_t S, size_t nblocks, const uint8_t* present, const uint8_t* required,
+                                            int data_only, int32_t* status_out, uint32_t* d_raw16_rows,
+                                            void* stream) try {
+    return mixed_dev_impl(c, d_shards, shard_stride, block_stride, S, nblocks, present, required, data_only, status_out,
+                          true, nullptr, nullptr, stream, d_raw16_rows);
+} catch (...) {
+    return rsmi::impl::exception_status();
+}
+
+int rsmi_reconstruct_mixed_batch_host_verify(rsmi_ctx* c, uint8_t* shards, size_t block_stride, size_t S, size_t nblocks,
+                                             const uint8_t* present, const uint8_t* required, int data_only,
+                                             int32_t* status_out, uint32_t* raw16_rows) try {
+    return mixed_host_impl(c, shards, block_stride, S, nblocks, present, required, data_only, status_out, true, nullptr,
+                           nullptr, raw16_rows);
 } catch (...) {
     return rsmi::impl::exception_status();
 }

@@ -96,6 +96,11 @@ def lib() -> ctypes.CDLL:
         "rsmi_reconstruct_mixed_batch_host_crcs": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, c_size, u8p, u8p,
                                                                   ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                                   ctypes.c_void_p]),
+        "rsmi_reconstruct_mixed_batch_dev_verify": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, c_size, c_size, u8p,
+                                                                   u8p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                                   ctypes.c_void_p]),
+        "rsmi_reconstruct_mixed_batch_host_verify": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, c_size, u8p, u8p,
+                                                                    ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
         "rsmi_crc_named_rows_dev": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, u8p, c_size, c_size, c_size, c_size,
                                                    ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                    ctypes.c_void_p]),
@@ -641,6 +646,32 @@ class Codec:
         st = (ctypes.c_int32 * max(nblocks, 1))() if status else None
         _check(lib().rsmi_reconstruct_mixed_batch_host_crcs(self._h, ptr, bs, S, nblocks, p, q, 1 if data_only else 0,
                                                             st, raw16_ptr or None, raw32_ptr or None))
+        return list(st)[:nblocks] if status else None
+
+    def reconstruct_mixed_batch_dev_verify(self, d_shards: int, rs: int, bs: int, S: int, nblocks: int, present,
+                                           required=None, data_only: bool = False, d_raw16_rows: int = 0,
+                                           stream: int = 0, status: bool = True) -> Optional[List[int]]:
+        """rsmi_reconstruct_mixed_batch_dev_verify: reconstruct_mixed_batch_dev plus R of every row it
+        read (a block's first k present rows) or rebuilt in d_raw16_rows[b*(k+m) + r] (uint32, device
+        memory, 0 elsewhere)."""
+        p, keep_p = self._masks(present, nblocks)
+        q, keep_q = self._masks(required, nblocks)
+        st = (ctypes.c_int32 * max(nblocks, 1))() if status else None
+        _check(lib().rsmi_reconstruct_mixed_batch_dev_verify(self._h, d_shards, rs, bs, S, nblocks, p, q,
+                                                             1 if data_only else 0, st, d_raw16_rows or None,
+                                                             stream or None))
+        return list(st)[:nblocks] if status else None
+
+    def reconstruct_mixed_batch_host_verify_ptr(self, ptr: int, bs: int, S: int, nblocks: int, present, required=None,
+                                                data_only: bool = False, raw16_rows_ptr: Optional[int] = None,
+                                                status: bool = True) -> Optional[List[int]]:
+        """rsmi_reconstruct_mixed_batch_host_verify on nblocks blocks of host memory at ptr; the raw
+        checksums land in host memory at raw16_rows_ptr (nblocks * (k+m) uint32)."""
+        p, keep_p = self._masks(present, nblocks)
+        q, keep_q = self._masks(required, nblocks)
+        st = (ctypes.c_int32 * max(nblocks, 1))() if status else None
+        _check(lib().rsmi_reconstruct_mixed_batch_host_verify(self._h, ptr, bs, S, nblocks, p, q,
+                                                              1 if data_only else 0, st, raw16_rows_ptr or None))
         return list(st)[:nblocks] if status else None
 
     def crc_named_rows_dev(self, d_data: int, data_rs: int, data_bs: int, d_parity: int, parity_rs: int,

@@ -44,7 +44,9 @@ extern "C" {
  * rsmi_locate_pair_checks), the pair heal (rsmi_heal_pair, rsmi_heal_pair_batch_host,
  * rsmi_heal_pair_batch_dev, rsmi_heal_pair_matrix), the scrub (rsmi_scrub, rsmi_scrub_batch_host,
  * rsmi_scrub_batch_dev) and the checksums of named rows (rsmi_crc_named_rows_dev,
- * rsmi_reconstruct_mixed_batch_dev_crcs, rsmi_reconstruct_mixed_batch_host_crcs). */
+ * rsmi_reconstruct_mixed_batch_dev_crcs, rsmi_reconstruct_mixed_batch_host_crcs) and the mixed
+ * reconstruct that checksums what it reads and writes (rsmi_reconstruct_mixed_batch_dev_verify,
+ * rsmi_reconstruct_mixed_batch_host_verify). */
 #define RSMI_ABI_VERSION 5
 
 typedef struct rsmi_ctx rsmi_ctx;
@@ -243,6 +245,42 @@ int rsmi_reconstruct_mixed_batch_host_crcs(rsmi_ctx* ctx, uint8_t* shards, size_
                                            size_t nblocks, const uint8_t* present, const uint8_t* required,
                                            int data_only, int32_t* status_out, uint32_t* raw16_out,
                                            uint32_t* raw32_out);
+
+/* rsmi_reconstruct_mixed_batch_dev (same arguments, checks in the same order with the same statuses,
+ * masks' lifetime, status_out and bytes written into the shards, the whole-batch
+ * RSMI_ERR_TOO_FEW_SHARDS before any launch when status_out == NULL included) plus R, the datanode's
+ * raw CRC-16, of every row the call touches, so a caller rebuilds no shard from a bad survivor
+ * unnoticed: the mixed form of rsmi_reconstruct_batch_host_verify.  d_raw16_rows (device memory,
+ * nblocks*(k+m) words, required: NULL -> RSMI_ERR_INVALID_ARG with the NULL checks) is zeroed on the
+ * stream first.  For a block with status RSMI_OK that has something to rebuild,
+ * d_raw16_rows[b*(k+m) + r] = R over bytes [0, S) of row r where the call touched that row:
+ *   rows it read     the first k present rows (rsmi_decode_matrix's used_rows for the block's mask),
+ *   rows it wrote    the wanted missing rows,
+ * and 0 for every other row of the block (present rows beyond the first k, missing rows that are
+ * not wanted).  Every row of a block the call does not touch -- one with nothing to rebuild, one with
+ * RSMI_ERR_TOO_FEW_SHARDS -- gets 0; a caller that wants those rows checked runs rsmi_crc16_rows_dev
+ * (host memory: rsmi_crc_rows_host) on them.  Each value is what rsmi_crc16_rows_dev gives for the
+ * row as it lies in memory after the call (a damaged survivor's R is that of its stored bytes), and
+ * rsmi_crc16_entry finishes it.  Padding may be read; it is never written and never reaches a
+ * checksum.  Where the shape has a kernel for it (k in {1,2,3,4,5,6,8,10,12,16}, at most 4 rows to
+ * rebuild in a block, rows 16-byte aligned or S >= 16) the checksums come from the one read of the
+ * survivors that rebuilds the rows; other blocks are rebuilt as above and their rows then read by
+ * rsmi_crc_named_rows_dev's kernels.  Stream-ordered, no sync (per-stream scratch grows as above);
+ * like _dev_crcs a batch with nothing to rebuild still needs the device to zero the output
+ * (RSMI_ERR_NO_DEVICE without one).  When the call fails as a whole the output is unspecified. */
+int rsmi_reconstruct_mixed_batch_dev_verify(rsmi_ctx* ctx, uint8_t* d_shards, size_t shard_stride,
+                                            size_t block_stride, size_t S, size_t nblocks, const uint8_t* present,
+                                            const uint8_t* required, int data_only, int32_t* status_out,
+                                            uint32_t* d_raw16_rows, void* stream);
+
+/* rsmi_reconstruct_mixed_batch_host plus the same checksums in host memory (raw16_rows,
+ * nblocks*(k+m) words, required), on each of its three paths.  On page-locked shards, which are
+ * coded where they lie, every survivor crosses PCIe once for both the rebuild and its checksum.  A
+ * batch with nothing to rebuild zeroes raw16_rows and returns RSMI_OK without a device; any other on
+ * a host without a GPU returns RSMI_ERR_NO_DEVICE.  Only wanted rows are written back. */
+int rsmi_reconstruct_mixed_batch_host_verify(rsmi_ctx* ctx, uint8_t* shards, size_t block_stride, size_t S,
+                                             size_t nblocks, const uint8_t* present, const uint8_t* required,
+                                             int data_only, int32_t* status_out, uint32_t* raw16_rows);
 
 /* Host-only, works without a GPU, like rsmi_decode_matrix: what the two calls above will do with
  * these masks.  Every output may be NULL.  status_out[b]: as above.  rows_out[b]: the rows the call
