@@ -256,6 +256,28 @@ struct MixedFusedKernelTable {
 const MixedFusedKernelTable& mixed_fused_kernels();
 void* mixed_scatter_kernel();
 
+// rsmi_encode_ragged_batch_* (rs_ragged_kernels.hip): rs_ragged_kernel per (K, MT), the K of the
+// coding kernels, aligned and unaligned-window blocks.  A launch codes the blocks of one class with
+// one tile of the encode plan; every block has its own shard size and its own rows.  Workgroup e
+// takes unit e: up to kRaggedUnitTiles consecutive 1 KiB-per-row tiles of one block, a tile per
+// wave.  The unit names its block's descriptor, which holds what a uniform launch takes as kernel
+// arguments: the block's first data and parity row, their row strides, S and its 16-byte chunks.
+constexpr int kRaggedUnitTiles = kFastWG / kWave;
+struct RaggedUnit {
+    uint32_t blk, tile;  // index into the launch's descriptors; the unit's first tile
+};
+struct alignas(16) RaggedBlockDev {
+    uint64_t data, parity;        // device addresses of data row 0 and parity row 0
+    uint64_t data_rs, parity_rs;  // row strides in bytes
+    uint32_t S, cpb;
+    uint32_t pad[6];
+};
+static_assert(sizeof(RaggedUnit) == 8 && sizeof(RaggedBlockDev) == 64, "what the kernels' scalar loads read");
+// the K with an rs_ragged_kernel (blocks of any other shape take launch_plan, one by one)
+constexpr bool ragged_shape(int K) { return K >= 1 && (K <= 6 || K == 8 || K == 10 || K == 12 || K == 16); }
+using RaggedKernelTable = StripeKernelTable;
+const RaggedKernelTable& ragged_kernels();
+
 // CRC-16 of shard rows (crc16.hpp): the device table buffer holds P[15][2][256] (the powers
 // A^(2^i), byte-sliced) and N[32][16] (u16); a wave folds kCrcSegTiles 1 KiB tiles of one row
 // with one N lookup per nibble (16-entry tables: each wave-wide lookup touches 8 distinct

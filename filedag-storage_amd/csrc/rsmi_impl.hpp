@@ -14,10 +14,11 @@
 //   rsmi_pair.cpp      rsmi_locate_pair: locate, then the pair of shards that explains an UNKNOWN block
 //   rsmi_heal_pair.cpp rsmi_heal_pair: locate pair, then the one or two named shards rewritten on the same stream
 //   rsmi_scrub.cpp     rsmi_scrub: Verify's flags and every shard's CRC-16 from one read of the rows
+//   rsmi_ragged.cpp    rsmi_encode_ragged_*: the encode of a batch whose blocks each have their own size
 // No CPU compute path anywhere: every byte of parity, reconstructed data or CRC and every verify
 // flag comes out of the HIP kernels (rs_kernels.hip, rs_kernels_tb.hip, rs_crc16_kernels.hip, rs_crc32_kernels.hip,
 // rs_verify_kernels.hip, rs_locate_kernels.hip, rs_heal_kernels.hip, rs_mixed_kernels.hip,
-// rs_mixed_fused_kernels.hip, rs_pair_kernels.hip, rs_heal_pair_kernels.hip, rs_scrub_kernels.hip).  Kernel headers: rs_gf_tile.hpp (the GF(2^8) tile pipeline), rs_verify_tile.hpp
+// rs_mixed_fused_kernels.hip, rs_pair_kernels.hip, rs_heal_pair_kernels.hip, rs_scrub_kernels.hip, rs_ragged_kernels.hip).  Kernel headers: rs_gf_tile.hpp (the GF(2^8) tile pipeline), rs_verify_tile.hpp
 // (the stripe checks' tile step), rs_crc_rows.hpp (what the CRC-16 and CRC-32 rows passes share).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -517,6 +518,23 @@ void classify_mixed(const rsmi_ctx* c, size_t nblocks, const uint8_t* present, c
 int launch_mixed(rsmi_ctx* c, const MixedBatch& mb, uint8_t* base, uint64_t rs, uint64_t bs, uint64_t S, uint64_t b0,
                  uint64_t nb, hipStream_t stream, uint32_t* d16 = nullptr, uint32_t* d32 = nullptr,
                  uint32_t* dver = nullptr);
+// need bytes of the stream's entry of ctx->mixed_scratch (rsmi_mixed.cpp; caller holds ctx->mu), 16-byte
+// aligned, at the same offset of the page-locked half h and the device half d: the moving head the
+// mixed reconstruct and the ragged encode share.  Waits for the stream once when the scratch has to
+// grow or start over; past 32 streams the device is drained once and every stream's scratch freed.
+int mixed_words(rsmi_ctx* c, hipStream_t st, size_t need, uint8_t*& h, uint8_t*& d);
+// rsmi_encode_ragged_batch_* (rsmi_ragged.cpp).  A block's class (RSMI_RAGGED_*) over these bases:
+// launch_plan's layout test on the block's two halves, and whether k has an rs_ragged_kernel.
+// tiles: the block's 1 KiB-per-row tiles, 0 for a fallback block.  Device-free.
+int ragged_class(const rsmi_ctx* c, uintptr_t data_base, uintptr_t parity_base, const rsmi_ragged_block& b,
+                 uint64_t& tiles);
+// The launches of a ragged batch (caller holds ctx->mu, the device is bound, the blocks have passed
+// the entry points' checks; data, parity: device addresses): per segment of whole blocks one upload
+// of the classes' units and the blocks' descriptors, rs_ragged_kernel per non-empty class (aligned,
+// then unaligned-window) and plan tile, launch_plan per fallback block behind them.  Stream-ordered,
+// no synchronisation unless the stream's scratch grows or starts over.
+int launch_ragged(rsmi_ctx* c, const Plan& plan, const uint8_t* data, uint8_t* parity, const rsmi_ragged_block* blocks,
+                  size_t nblocks, hipStream_t stream);
 int ensure_crc_tables(rsmi_ctx* c);
 int ensure_crc32_tables(rsmi_ctx* c);
 // R(row) / R32(row) of the rows the plan rebuilt (want && !present), one row per block at

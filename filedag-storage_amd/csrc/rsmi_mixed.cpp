@@ -84,9 +84,11 @@ rsmi_ctx::MixedScratch& mixed_scratch(rsmi_ctx* c, hipStream_t st) {
     return map[st];
 }
 
+}  // namespace
+
 // need bytes of the stream's scratch, 16-byte aligned, at the same offset of both halves; they
 // stay untouched until the stream has been waited for.  Waits for the stream once when the
-// scratch has to grow or start over.
+// scratch has to grow or start over.  (Shared with the ragged encode, rsmi_ragged.cpp.)
 int mixed_words(rsmi_ctx* c, hipStream_t st, size_t need, uint8_t*& h, uint8_t*& d) {
     rsmi_ctx::MixedScratch& ms = mixed_scratch(c, st);
     need = round_up(need, 16);
@@ -110,6 +112,8 @@ int mixed_words(rsmi_ctx* c, hipStream_t st, size_t need, uint8_t*& h, uint8_t*&
     ms.head += need;
     return RSMI_OK;
 }
+
+namespace {
 
 // One class of a segment on the _verify route: rs_mixed_fused_kernel over the class's units, a
 // workgroup each (at most the class's tiles, so within option launch_units_max as the segment is),

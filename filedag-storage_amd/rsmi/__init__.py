@@ -36,6 +36,17 @@ ErrHost = 102
 LocateClean = -1
 LocateUnknown = -2
 
+# what the ragged encode does with a block (include/rsmi.h RSMI_RAGGED_*)
+RaggedAligned = 0
+RaggedUA = 1
+RaggedFallback = 2
+
+
+class RaggedBlock(ctypes.Structure):
+    """include/rsmi.h rsmi_ragged_block: one block of a ragged encode."""
+    _fields_ = [("S", ctypes.c_uint64), ("data_off", ctypes.c_uint64), ("data_shard_stride", ctypes.c_uint64),
+                ("parity_off", ctypes.c_uint64), ("parity_shard_stride", ctypes.c_uint64)]
+
 
 class RsmiError(Exception):
     def __init__(self, code: int, msg: str = ""):
@@ -107,6 +118,11 @@ def lib() -> ctypes.CDLL:
         "rsmi_reconstruct_mixed_classify": (ctypes.c_int, [ctypes.c_void_p, c_size, u8p, u8p, ctypes.c_int,
                                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                            ctypes.POINTER(c_size)]),
+        "rsmi_encode_ragged_batch_dev": (ctypes.c_int, [ctypes.c_void_p, u8p, u8p, ctypes.c_void_p, c_size,
+                                                        ctypes.c_void_p]),
+        "rsmi_encode_ragged_batch_host": (ctypes.c_int, [ctypes.c_void_p, u8p, u8p, ctypes.c_void_p, c_size]),
+        "rsmi_encode_ragged_classify": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_void_p, c_size, ctypes.c_void_p, ctypes.c_void_p]),
         "rsmi_verify_batch_dev": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, c_size, u8p, c_size, c_size, c_size, c_size,
                                                  ctypes.c_void_p, ctypes.c_void_p]),
         "rsmi_verify_batch_host": (ctypes.c_int, [ctypes.c_void_p, u8p, c_size, u8p, c_size, c_size, c_size,
@@ -684,6 +700,45 @@ class Codec:
                                              nblocks, d_rows or None, slots, d_raw16 or None, d_raw32 or None,
                                              stream or None))
 
+    # -- ragged batches: a size and a place per block (rsmi_encode_ragged_*).  blocks is a sequence of
+    # (S, data_off, data_shard_stride, parity_off, parity_shard_stride), a numpy array of shape
+    # (nblocks, 5) and dtype uint64, a ctypes array of RaggedBlock, or (address, nblocks).
+    @staticmethod
+    def _ragged(blocks):
+        """(address or None, nblocks, the object that keeps the descriptors alive)."""
+        if isinstance(blocks, tuple) and len(blocks) == 2 and all(isinstance(x, int) for x in blocks):
+            return blocks[0] or None, blocks[1], None
+        if isinstance(blocks, ctypes.Array):
+            return (ctypes.addressof(blocks) if len(blocks) else None), len(blocks), blocks
+        if hasattr(blocks, "ctypes") and hasattr(blocks, "dtype"):
+            if blocks.ndim != 2 or blocks.shape[1] != 5 or blocks.dtype.itemsize != 8 or not blocks.flags["C_CONTIGUOUS"]:
+                raise RsmiError(ErrInvalidArg, "ragged blocks need a contiguous (nblocks, 5) uint64 array")
+            return (blocks.ctypes.data if blocks.shape[0] else None), blocks.shape[0], blocks
+        arr = (RaggedBlock * max(len(blocks), 1))()
+        for i, b in enumerate(blocks):
+            arr[i] = RaggedBlock(*[int(x) for x in b])
+        return ctypes.addressof(arr), len(blocks), arr
+
+    def encode_ragged_batch_dev(self, d_data: int, d_parity: int, blocks, stream: int = 0) -> None:
+        """rsmi_encode_ragged_batch_dev: the encode of blocks that each have their own shard size and
+        rows, device-resident, stream-ordered.  The descriptors are read before the call returns."""
+        p, nb, keep = self._ragged(blocks)
+        _check(lib().rsmi_encode_ragged_batch_dev(self._h, d_data or None, d_parity or None, p, nb, stream or None))
+
+    def encode_ragged_batch_host_ptr(self, data_ptr: int, parity_ptr: int, blocks) -> None:
+        """rsmi_encode_ragged_batch_host: the same descriptors over host bases."""
+        p, nb, keep = self._ragged(blocks)
+        _check(lib().rsmi_encode_ragged_batch_host(self._h, data_ptr or None, parity_ptr or None, p, nb))
+
+    def encode_ragged_classify(self, data_base: int, parity_base: int, blocks):
+        """rsmi_encode_ragged_classify, device-free: (the blocks' classes, Ragged*; their 1 KiB-per-row
+        tiles per plan tile, 0 for a fallback block).  The bases count for their alignment only."""
+        p, nb, keep = self._ragged(blocks)
+        cls = (ctypes.c_uint8 * max(nb, 1))()
+        tiles = (ctypes.c_uint64 * max(nb, 1))()
+        _check(lib().rsmi_encode_ragged_classify(self._h, data_base or None, parity_base or None, p, nb, cls, tiles))
+        return list(cls)[:nb], list(tiles)[:nb]
+
     def reconstruct_mixed_classify(self, nblocks: int, present, required=None, data_only: bool = False):
         """rsmi_reconstruct_mixed_classify, device-free: (statuses, rows written per block, the
         blocks' pattern indices by first appearance, the number of patterns)."""
@@ -843,6 +898,40 @@ class Erasure:
         flat = self.encoder().encode_block(data)
         S = len(flat) // n
         return [flat[i * S:(i + 1) * S] for i in range(n)]
+
+    def encode_data_many(self, blocks: List[bytes]) -> List[List[Optional[bytes]]]:
+        """encode_data for many blocks at once, each of its own length, through one
+        rsmi_encode_ragged_batch_host call: the result equals [encode_data(b) for b in blocks] (an
+        empty block gives k + m times None, as there).  The Split of every non-empty block (shard
+        size ceilFrac(len, k), the last data shards zero-padded) is done here into one buffer, a
+        block's k + m rows side by side at pitch roundup(S, 16)."""
+        k, n = self.data_blocks, self.data_blocks + self.parity_blocks
+        out: List[List[Optional[bytes]]] = [[None] * n for _ in blocks]
+        work = []  # (block index, S, pitch, offset of the block's rows)
+        total = 0
+        for bi, data in enumerate(blocks):
+            if len(data) == 0:
+                continue
+            S = ceil_frac(len(data), k)
+            P = (S + 15) // 16 * 16
+            work.append((bi, S, P, total))
+            total += n * P
+        if not work:
+            return out
+        flat = bytearray(total)
+        for bi, S, P, off in work:
+            data = blocks[bi]
+            for i in range(k):
+                row = data[i * S:(i + 1) * S]
+                flat[off + i * P:off + i * P + len(row)] = row
+        desc = (RaggedBlock * len(work))()
+        for j, (bi, S, P, off) in enumerate(work):
+            desc[j] = RaggedBlock(S, off, P, off + k * P, P)
+        base = ctypes.addressof(_buf(flat))
+        self.encoder().encode_ragged_batch_host_ptr(base, base, desc)
+        for bi, S, P, off in work:
+            out[bi] = [bytes(flat[off + i * P:off + i * P + S]) for i in range(n)]
+        return out
 
     def _reconstruct(self, shards: List[Optional[bytes]], data_only: bool) -> None:
         n = self.data_blocks + self.parity_blocks

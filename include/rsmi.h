@@ -46,7 +46,8 @@ extern "C" {
  * rsmi_scrub_batch_dev) and the checksums of named rows (rsmi_crc_named_rows_dev,
  * rsmi_reconstruct_mixed_batch_dev_crcs, rsmi_reconstruct_mixed_batch_host_crcs) and the mixed
  * reconstruct that checksums what it reads and writes (rsmi_reconstruct_mixed_batch_dev_verify,
- * rsmi_reconstruct_mixed_batch_host_verify). */
+ * rsmi_reconstruct_mixed_batch_host_verify) and the ragged encode (rsmi_encode_ragged_batch_dev,
+ * rsmi_encode_ragged_batch_host, rsmi_encode_ragged_classify). */
 #define RSMI_ABI_VERSION 5
 
 typedef struct rsmi_ctx rsmi_ctx;
@@ -291,6 +292,66 @@ int rsmi_reconstruct_mixed_batch_host_verify(rsmi_ctx* ctx, uint8_t* shards, siz
 int rsmi_reconstruct_mixed_classify(const rsmi_ctx* ctx, size_t nblocks, const uint8_t* present,
                                     const uint8_t* required, int data_only, int32_t* status_out, uint8_t* rows_out,
                                     uint32_t* pattern_out, size_t* npatterns_out);
+
+/* ------------------------------------------------------------------ ragged batches: a size per block */
+
+/* The encode calls above take one S for the whole batch.  A Dag Node's blocks do not share a size:
+ * a file is a run of full chunks, one tail chunk of any length and a few small link nodes.  These
+ * calls encode such a batch in one go, with no sort of the blocks by size and no call per size.
+ *   Blocks.  blocks holds nblocks descriptors in HOST memory.  They are read before the call
+ *   returns: the caller may free or overwrite them at once, also after the stream-ordered _dev call.
+ *   Data row c of a block is at data_base + data_off + c*data_shard_stride, parity row j at
+ *   parity_base + parity_off + j*parity_shard_stride; the two halves are independent.  A block's
+ *   parity rows must not overlap any row of any block; data rows may be shared between blocks.
+ *   What is written.  For every block, bytes [0, S) of its m parity rows, and they are the bytes
+ *   rsmi_encode_batch_dev writes for that block alone (nblocks = 1) at the same addresses and
+ *   strides.  Nothing else is written: no data row, no byte at or past S of any row, no byte of a
+ *   gap.  The layout contract holds: padding may be read and is never written.
+ *   Arguments.  All checks come before any device access: a NULL ctx, base or blocks ->
+ *   RSMI_ERR_INVALID_ARG; nblocks == 0 -> RSMI_OK; then the blocks in index order, the first bad
+ *   block deciding the status, per block in the order of rsmi_encode_batch_dev: S == 0 ->
+ *   RSMI_ERR_SHARD_NO_DATA, then a shard stride below S -> RSMI_ERR_INVALID_ARG.  Nothing is
+ *   written when a call fails on its arguments; on a host without a GPU a call that passes them
+ *   returns RSMI_ERR_NO_DEVICE.
+ * The calls are joined to ABI version 5 (additive); none of them takes or clears the per-thread
+ * wait hook. */
+typedef struct rsmi_ragged_block {
+    uint64_t S;                   /* this block's shard size, > 0 */
+    uint64_t data_off;            /* data row c   at d_data   + data_off   + c * data_shard_stride   */
+    uint64_t data_shard_stride;
+    uint64_t parity_off;          /* parity row j at d_parity + parity_off + j * parity_shard_stride */
+    uint64_t parity_shard_stride;
+} rsmi_ragged_block;
+
+/* What the device call does with a block (rsmi_encode_ragged_classify). */
+#define RSMI_RAGGED_ALIGNED 0  /* rows 16-byte aligned, strides multiples of 16 and >= S rounded up to 16 */
+#define RSMI_RAGGED_UA 1       /* any other rows of at least 16 bytes: the unaligned-window kernels    */
+#define RSMI_RAGGED_FALLBACK 2 /* S < 16 on unaligned rows, k not in {1..6,8,10,12,16}, S >= 2^31:
+                                * rsmi_encode_batch_dev's launch for that block alone               */
+
+/* Device-resident.  Stream-ordered, no sync: the blocks' descriptors travel to per-stream scratch
+ * on the same stream (growing it, or starting it over once it is used up, waits for that stream
+ * once).  One launch per class of blocks (aligned, unaligned-window) and tile of the encode plan
+ * (m > 4: several), whatever the number of distinct sizes; fallback blocks are launched one by one
+ * behind them. */
+int rsmi_encode_ragged_batch_dev(rsmi_ctx* ctx, const uint8_t* d_data, uint8_t* d_parity,
+                                 const rsmi_ragged_block* blocks, size_t nblocks, void* stream);
+
+/* The same descriptors over host bases; the rows are already Split, as for rsmi_encode_batch_host.
+ * With both halves page-locked (rsmi_host_alloc) the rows are coded where they lie; otherwise they
+ * are staged through page-locked memory by CPU copies, in chunks of whole blocks, and only bytes
+ * [0, S) of the parity rows are copied back. */
+int rsmi_encode_ragged_batch_host(rsmi_ctx* ctx, const uint8_t* data, uint8_t* parity,
+                                  const rsmi_ragged_block* blocks, size_t nblocks);
+
+/* Host-only, works without a GPU: what rsmi_encode_ragged_batch_dev will do with each block of these
+ * descriptors over these bases.  class_out[b] (may be NULL): RSMI_RAGGED_*.  tiles_out[b] (may be
+ * NULL): the block's 1 KiB-per-row tiles per tile of the encode plan, 0 for a fallback block.  The
+ * base pointers are used for their alignment only and are never dereferenced (they may be NULL).
+ * The blocks pass the calls' checks first, with their statuses. */
+int rsmi_encode_ragged_classify(const rsmi_ctx* ctx, const void* data_base, const void* parity_base,
+                                const rsmi_ragged_block* blocks, size_t nblocks, uint8_t* class_out,
+                                uint64_t* tiles_out);
 
 /* ------------------------------------------------------------------ Encoder.Verify */
 
