@@ -22,6 +22,7 @@
 
 #include "crc16.hpp"
 #include "rs_crc16_device.hpp"
+#include "rs_crc_fold.hpp"
 #include "rs_device.hpp"
 #include "rs_gf_tile.hpp"
 #include "rs_plan.hpp"
@@ -374,34 +375,14 @@ __launch_bounds__(kFastWG, WPS) void rs_fast_kernel(const RsPlanDev* __restrict_
 // DagNode.Put's device form (node.go:358-408 with server.go:57-80's checksum of every shard):
 // the encode of rs_fast_kernel (aligned layouts, encode plans: input row c is shard c, output row
 // j shard K + j) with R(shard) of every row it reads and writes folded on the matrix cores
-// instead of the nibble tables of the CRC variants above.  R(chunk) is GF(2)-linear in the
-// chunk's 128 bits, so a tile's fold is a GF(2) matrix product evaluated as exact fp4 counts
-// (v_mfma_scale_f32_16x16x128_f8f6f4, as in rs_crc16_rows_mfma_kernel): B = one data bit per
-// nibble (forms x & 0x11111111, & 0x22.., & 0x44.. and (x >> 3) & 0x11111111 -- the encode
-// computes x >> 3 for its GF tables anyway), A = the weights of the tile's position in its unit
-// (crc16.hpp FW, loaded once per tile and shared by every row).  Per row and tile: 4
-// bitwise ops per dword and 4 MFMAs, against 15 VALU and 8 LDS lookups per dword for the nibble
-// fold.
-//
-// A unit is kFusedUnitTiles = 4 consecutive tiles of one block, coded by the 4 waves of one
-// workgroup (one tile each), and the counts of a row accumulate over the unit's tiles, so the
-// parity is read once per unit.  Two shards share
-// one f32 accumulator: the odd shard's MFMAs run with B scale 2^12, and a unit's counts stay
-// below 2^11 (4 tiles x 4 MFMAs x 128 products), so count0 + 2^12 count1 < 2^24 is exact in f32
-// and the parities are bits 0 and 12 of the integer.  Record of a unit: per accumulator and lane
-// l = 16 j + m, a byte whose bits 0-3 / 4-7 = parity of element i of the even / odd shard (CRC
-// bit 4 j + i of class m: chunks m, m + 16, m + 32, m + 48 of the unit's tiles, relative to the
-// end of chunk 48 + m of its last tile); four accumulators per dword, dword d of the unit at lane
-// slot 4 m + j, so a class's four dwords are contiguous for rs_crc16_combine_mfma_kernel.
+// instead of the nibble tables of the CRC variants above.  The fold is rs_crc_fold.hpp's (the fp4
+// forms, the two shards to an accumulator, the unit's record and the UA correction are told
+// there): a unit is kFusedUnitTiles = 4 consecutive tiles of one block, coded by the 4 waves of
+// one workgroup (one tile each), and the waves' counts meet in LDS at the unit's end.
 //
 // UA: rows at any alignment and pitch (S >= 16; the Split layout), with the unaligned-window
-// loads and stores of rs_fast_kernel's UA form.  The fold needs every lane's bytes at their
-// chunk position: only the lane holding a row's last, overlapping window (it starts at S - 16,
-// not at 16 ch) differs: its window must move right by d = 16 ch - (S - 16) bytes.  The rows go
-// into the fold unshifted, and the row's last tile then adds (window XOR shifted window) of that
-// lane alone (the counts only matter mod 2), for the output rows from registers and for the input
-// rows from a reload, so the common tiles carry none of it.  Workgroups take XCD-contiguous units,
-// as the UA coding kernels do.
+// loads and stores of rs_fast_kernel's UA form.  Workgroups take XCD-contiguous units, as the UA
+// coding kernels do.
 // INL (small launches, a block of a few units): the block's last unit to finish combines its
 // records into R(row) itself, so the call needs no second launch (below).
 // TB: over a table of block bases, as rs_fast_kernel TB (a coalesced group of DagNode.Put
@@ -443,18 +424,15 @@ __global__ __launch_bounds__(kWG, WPS) void rs_fused_mfma_kernel(const RsPlanDev
     const uint32_t lane = threadIdx.x & (kWave - 1);
     const uint32_t wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     // a workgroup codes a unit, wave w its tile w: every wave codes one tile, as in the plain
-    // encode, and the waves' counts meet in LDS at the end (below); UA: each XCD takes one
-    // contiguous eighth of the units (their rows share boundary lines)
-    const uint32_t u =
-        UA ? tile_group(blockIdx.x, gridDim.x, (gridDim.x & 7u) ? 0u : gridDim.x) : uint32_t(blockIdx.x);
+    // encode, and the waves' counts meet in LDS at the end (below)
+    const uint32_t u = fold_unit<UA>();
     if (u >= nunits) {
         stage();
         launch_done<TB>(bases);
         return;
     }
-    const uint32_t blk = u / upb;
-    const uint32_t t0 = (u - blk * upb) * kFusedUnitTiles;
-    const uint32_t nt = tpb - t0 < uint32_t(kFusedUnitTiles) ? tpb - t0 : uint32_t(kFusedUnitTiles);
+    const FoldUnit un = fold_unit_tiles(u, upb, tpb);
+    const uint32_t blk = un.blk, t0 = un.t0, nt = un.nt;
     const uint8_t* ib = block_rows<TB>(bases, in, blk, in_bs);
     uint8_t* ob = block_rows<TB>(bases, out, blk, out_bs);
 
@@ -465,9 +443,8 @@ __global__ __launch_bounds__(kWG, WPS) void rs_fused_mfma_kernel(const RsPlanDev
 #pragma unroll
     for (int j = 0; j < MT; j++) out_off[j] = uint64_t(plan->out_row[j]) * out_rs;
 
-    mfma_v4f cacc[NACC];
-#pragma unroll
-    for (int a = 0; a < NACC; a++) cacc[a] = mfma_v4f{0.f, 0.f, 0.f, 0.f};
+    CrcFold<NACC> fold;
+    fold.clear();
 
     // the output rows of one tile: the lane's chunk ch (UA: its window at byte win)
     auto store_out = [&](uint32_t ch, uint32_t win, const uint32_t (&acc)[MT][4]) {
@@ -487,59 +464,7 @@ __global__ __launch_bounds__(kWG, WPS) void rs_fused_mfma_kernel(const RsPlanDev
     for (uint32_t i = wid; i < nt; i += kWG / kWave) {
         const LaneChunk lc = lane_chunk<UA>(t0 + i, lane, cpb, S);
         const uint32_t ch = lc.ch, chl = lc.chl, win = lc.win;
-        const bool last_tile = (t0 + i + 1) * uint32_t(kWave * 16) > S;  // wave-uniform
-        // UA: the last window's shift to its chunk position (0 when S is a multiple of 16)
-        const uint32_t dsh = UA ? 16u * (cpb - 1u) - (S - 16u) : 0u;
-        // wave-uniform: this tile's last window moves
-        const bool fix = UA && last_tile && dsh != 0u;
-        const bool mine = ch == cpb - 1u;
-        // the window's 16 bytes shifted right by dsh bytes (1..15, zero fill): two u64 halves
-        auto shifted = [&](const u32x4& x) -> u32x4 {
-            const uint64_t lo = uint64_t(x[0]) | (uint64_t(x[1]) << 32), hi = uint64_t(x[2]) | (uint64_t(x[3]) << 32);
-            const uint32_t sb = 8u * dsh;
-            const uint64_t nlo = sb == 0u ? lo : sb < 64u ? (lo >> sb) | (hi << ((64u - sb) & 63u)) : hi >> ((sb - 64u) & 63u);
-            const uint64_t nhi = sb < 64u ? hi >> sb : 0u;
-            return u32x4{uint32_t(nlo), uint32_t(nlo >> 32), uint32_t(nhi), uint32_t(nhi >> 32)};
-        };
-        // the correction that moves the window's bytes to their chunk position: the counts only
-        // matter mod 2, so adding (window XOR shifted window), its lane alone, does it
-        auto correction = [&](const u32x4& x) -> u32x4 {
-            const u32x4 y = shifted(x);
-            return u32x4{mine ? x[0] ^ y[0] : 0u, mine ? x[1] ^ y[1] : 0u, mine ? x[2] ^ y[2] : 0u, mine ? x[3] ^ y[3] : 0u};
-        };
-        // bytes of the lane's chunk that count: those before S (lanes past the row's last chunk,
-        // which loaded a clamped chunk, count nothing); all-ones except in a row's last tile
-        uint32_t mk[4] = {~0u, ~0u, ~0u, ~0u};
-        if (last_tile) {
-            const int valid = int(S) - int(ch * 16u);
-#pragma unroll
-            for (int w = 0; w < 4; w++) mk[w] = bytes_mask(valid - 4 * w);
-        }
-        // this tile position's weights, one operand per bit form, shared by every row
-        // (from global memory: the 16 KiB table stays in the L2, and a workgroup that staged it
-        // in LDS first would hold its waves' HBM loads back by the staging's latency)
-        const u32x4* wt = reinterpret_cast<const u32x4*>(crc_tbl + kCrcFWOff) + (4 - kFusedUnitTiles + i) * 4 * kWave + lane;
-        u32x4 W[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) W[q] = wt[q * kWave];
-        // one MFMA: bit form q of row r's chunk x into the row's accumulator
-        auto crc_mfma = [&](const u32x4& x, int r, int q) {
-            mfma_v4f& acc = cacc[r / 2];
-            const uint32_t msk = q == 1 ? 0x22222222u : q == 2 ? 0x44444444u : 0x11111111u;
-            mfma_v8i bd;
-#pragma unroll
-            for (int w = 0; w < 4; w++)
-                bd[w] = int(__builtin_amdgcn_bitop3_b32(q < 3 ? x[w] : x[w] >> 3, mk[w], msk, 0x80));  // a & b & c
-            bd[4] = bd[5] = bd[6] = bd[7] = 0;
-            const u32x4 Wq = W[q];
-            const mfma_v8i aw = {int(Wq[0]), int(Wq[1]), int(Wq[2]), int(Wq[3]), 0, 0, 0, 0};
-            acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(aw, bd, acc, 4, 4, 0, 127, 0,
-                                                                   (r & 1) ? 127 + 12 : 127);
-        };
-        // keep the MFMAs where they are issued: the accumulators are only read after the tile
-        // loop, so without an anchor the MFMAs sink to the loop's end and every row's bit forms
-        // stay live
-        auto anchor = [&](int r) { asm volatile("" : "+v"(cacc[r / 2])); };
+        fold.template tile_setup<UA>(t0 + i, i, lane, cpb, S, crc_tbl);
         auto load_col = [&](int c) {
             if constexpr (UA)
                 return ld16u<NT == 1>(ib + in_off[c] + win);
@@ -557,35 +482,17 @@ __global__ __launch_bounds__(kWG, WPS) void rs_fused_mfma_kernel(const RsPlanDev
             // form w's MFMA between the GF work of dword w and w + 1: its latency (and the
             // chain of the row's four MFMAs) hides under this wave's own VALU stream
             [&](int c, int w, const u32x4& x) {
-                crc_mfma(x, c, w);
+                fold.mfma(x, c, w);
                 __builtin_amdgcn_sched_barrier(0);
             },
-            [&](int c, const u32x4&) { anchor(c); },
+            [&](int c, const u32x4&) { fold.anchor(c); },
             [&](int c, u32x4& x) {
                 if (c + P < K) x = load_col(c + P);
             });
-        // the output rows: bit form by bit form, even rows before odd ones, so consecutive MFMAs
-        // go to different accumulators wherever two output rows do not share one
-#pragma unroll
-        for (int q = 0; q < 4; q++)
-#pragma unroll
-            for (int h = 0; h < 2; h++)
-#pragma unroll
-                for (int j = h; j < MT; j += 2) crc_mfma(u32x4{acc[j][0], acc[j][1], acc[j][2], acc[j][3]}, K + j, q);
-#pragma unroll
-        for (int j = 0; j < MT; j++) anchor(K + j);
-        // UA: every row's last window went in unshifted; correct the output rows' counts here
-        // and the input rows' after the stores (reloaded: a shifted copy of every row in flight
-        // would not fit the registers)
-        if (UA && fix) {
-#pragma unroll
-            for (int j = 0; j < MT; j++) {
-                const u32x4 d = correction(u32x4{acc[j][0], acc[j][1], acc[j][2], acc[j][3]});
-#pragma unroll
-                for (int q = 0; q < 4; q++) crc_mfma(d, K + j, q);
-                anchor(K + j);
-            }
-        }
+        // the output rows' pass before the stores; UA: every row's last window went in unshifted:
+        // the output rows' counts are corrected here, the input rows' after the stores
+        fold.template rows<K, MT>(acc);
+        if (UA && fold.fix) fold.template fix_rows<K, MT>(acc);
 
         if constexpr (INL) {
 #pragma unroll
@@ -597,42 +504,11 @@ __global__ __launch_bounds__(kWG, WPS) void rs_fused_mfma_kernel(const RsPlanDev
         } else {
             store_out(ch, win, acc);
         }
-        if (UA && fix) {
-            // an opaque base: the reloads must not be merged with the row loop's loads (that
-            // would keep every row's window live through the tile)
-            const uint8_t* rb = ib;
-            uint32_t rw = win;
-            asm volatile("" : "+s"(rb), "+v"(rw));
-#pragma unroll
-            for (int c = 0; c < K; c++) {
-                u32x4 x = {0u, 0u, 0u, 0u};
-                if (mine) x = ld16u<NT == 1>(rb + in_off[c] + rw);  // that lane's 16 bytes only
-                const u32x4 d = correction(x);
-#pragma unroll
-                for (int q = 0; q < 4; q++) crc_mfma(d, c, q);
-                anchor(c);  // one reload at a time
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
+        if (UA && fold.fix) fold.template fix_reload<K, NT == 1>(ib, in_off, win);
     }
     stage();  // waves without a tile (the unit's last tiles past the row's end)
 
-    // parities -> the unit's record: byte (accumulator a, lane slot), bits i / 4 + i = element i's
-    // parity of shard 2 a / 2 a + 1 (bits 0 and 12 of the exact count)
-    auto record = [&](int a, const mfma_v4f& c) {
-        uint32_t y = 0;
-#pragma unroll
-        for (int e = 0; e < 4; e++) y |= (uint32_t(c[e]) & 0x1001u) << e;
-        crc_rec[(uint64_t(u) * NACC + a) * kWave + (lane & 15u) * 4u + (lane >> 4)] = uint8_t(y | (y >> 8));
-    };
-    // the unit's four tiles meet in LDS (count sums stay below 2^24: exact), and wave w reads out
-    // accumulators w, w + 4, ..., so no wave is left with the whole unit's tail
-    __shared__ mfma_v4f s_red[kWG / kWave][NACC][kWave];
-#pragma unroll
-    for (int a = 0; a < NACC; a++) s_red[wid][a][lane] = cacc[a];
-    __syncthreads();
-    for (int a = int(wid); a < NACC; a += kWG / kWave)
-        record(a, s_red[0][a][lane] + s_red[1][a][lane] + s_red[2][a][lane] + s_red[3][a][lane]);
+    fold.finish(u, wid, lane, crc_rec);
     if constexpr (INL) {
         // The block's last unit to finish combines its records into R(row) (no second launch).
         // Each workgroup publishes its record (fence, then one atomic increment of the block's

@@ -214,6 +214,26 @@ int launch_crc_named(rsmi_ctx* c, const NamedRowsArgs& a, uint64_t S, uint64_t n
     return hip_status(hipGetLastError());
 }
 
+FoldGeometry::FoldGeometry(uint64_t S, uint64_t nsh_)
+    : cpb((S + 15) / 16), tpb((cpb + kWave - 1) / kWave), upb((tpb + kFusedUnitTiles - 1) / kFusedUnitTiles),
+      nsh(nsh_), nacc((nsh_ + 1) / 2), rec_per_block(upb * nacc * kWave) {
+    const int64_t unit_bytes = int64_t(kFusedUnitTiles) * kWave * 16;
+    const uint64_t e = uint64_t(((int64_t(S) - int64_t(upb) * unit_bytes) % int64_t(kCrcOrder) + kCrcOrder) % kCrcOrder);
+    for (int b = 0; b < 16; b++) sh.col[b] = crc16_tables().shift(uint16_t(1u << b), e);
+}
+
+int launch_fold_combine(rsmi_ctx* c, const uint8_t* rec, const FoldGeometry& g, uint64_t nitems, uint32_t* out,
+                        hipStream_t stream) {
+    const uint32_t* ctb = c->d_crc_tbl;
+    uint32_t upb32 = uint32_t(g.upb), nacc32 = uint32_t(g.nacc), nsh32 = uint32_t(g.nsh);
+    Crc16Shift sh = g.sh;
+    void* args[] = {&ctb, &rec, &upb32, &nacc32, &nsh32, &sh, &nitems, &out};
+    const uint64_t items = nitems * ((g.nsh + 3) / 4);
+    const uint32_t grid = uint32_t(
+        std::max<uint64_t>(1, std::min<uint64_t>((items + 3) / 4, uint64_t(c->num_cu) * RSMI_COMBINE_WGS_PER_CU)));
+    return hip_status(hipLaunchKernel(crc16_combine_mfma_kernel(), dim3(grid), dim3(kWG), args, 0, stream));
+}
+
 // Any single-tile plan with the CRC-16 fused in (rs_fast_kernel CRC variants), then R(row) of
 // its K input rows and MT output rows into raw[b * (K + MT) + r] (input row c at r = c, output
 // row j at r = K + j; device or page-locked host memory).  Needs K <= 16, one plan tile
@@ -248,9 +268,8 @@ int launch_plan_crc(rsmi_ctx* c, const Plan& plan, const uint8_t* in, size_t in_
     if ((mfma_fn || tb_inl) && c->opt_fused_fold == 1) {
         // the fold on the matrix cores (rs_fused_mfma_kernel): a unit of 4 tiles per workgroup,
         // then the records' combine
-        const size_t upb = (tpb + kFusedUnitTiles - 1) / kFusedUnitTiles;
-        const size_t nacc = (nsh + 1) / 2;  // two-shard accumulators: a record byte per lane each
-        const size_t rec_per_block = upb * nacc * kWave;
+        const FoldGeometry g(S, nsh);
+        const uint64_t upb = g.upb, rec_per_block = g.rec_per_block;
         // launches of at most launch_units_max units (a workgroup each); a table is never cut (its
         // entries are bases, not a range): one launch, or the callers' fallback
         const uint64_t max_blocks = std::max<uint64_t>(1, uint64_t(c->opt_launch_units_max) / upb);
@@ -263,11 +282,7 @@ int launch_plan_crc(rsmi_ctx* c, const Plan& plan, const uint8_t* in, size_t in_
         uint32_t S32 = uint32_t(S), cpb32 = uint32_t(cpb), tpb32 = uint32_t(tpb), upb32 = uint32_t(upb);
         const uint32_t* ctb = c->d_crc_tbl;
         uint64_t ibs = in_bs, irs = in_rs, obs = out_bs, ors = out_rs;
-        // A^e moves a row's value from the end of its last unit to the row's end
-        const int64_t unit_bytes = int64_t(kFusedUnitTiles) * kWave * 16;
-        const uint64_t e = uint64_t(((int64_t(S) - int64_t(upb) * unit_bytes) % int64_t(kCrcOrder) + kCrcOrder) % kCrcOrder);
-        Crc16Shift sh;
-        for (int b = 0; b < 16; b++) sh.col[b] = crc16_tables().shift(uint16_t(1u << b), e);
+        Crc16Shift sh = g.sh;
         // a launch of a few units (the per-block calls of DagNode.Put) combines in the kernel: one
         // launch instead of two; big ones keep the separate combine (rs_fused_mfma_kernel INL)
         void* inl_fn = aligned ? (tb ? kt.fused_inl_tb : kt.fused_inl)[tile.K][tile.MT]
@@ -312,20 +327,8 @@ int launch_plan_crc(rsmi_ctx* c, const Plan& plan, const uint8_t* in, size_t in_
             HIP_TRY(hipLaunchKernel(fn, dim3(nunits), dim3(kWG), args, 0, st));  // a workgroup per unit
             c->split_launches.fetch_add(1, std::memory_order_relaxed);
         }
-        if (!inline_combine) {
-            uint32_t nacc32 = uint32_t(nacc), nsh32 = uint32_t(nsh);
-            uint64_t nb64 = nblocks;
-            const uint8_t* crec = rec;
-            void* cargs[] = {&ctb, &crec, &upb32, &nacc32, &nsh32, &sh, &nb64, &raw};
-            // a persistent grid of up to 8 workgroups per CU, 4 waves each, over (block, 4-row group) items
-            const uint64_t items = nblocks * ((nsh + 3) / 4);
-#ifndef RSMI_COMBINE_WGS_PER_CU
-#define RSMI_COMBINE_WGS_PER_CU 8
-#endif
-            const uint32_t grid = uint32_t(std::max<uint64_t>(
-                1, std::min<uint64_t>((items + 3) / 4, uint64_t(c->num_cu) * RSMI_COMBINE_WGS_PER_CU)));
-            HIP_TRY(hipLaunchKernel(crc16_combine_mfma_kernel(), dim3(grid), dim3(kWG), cargs, 0, st));
-        }
+        if (!inline_combine)
+            if ((rc = launch_fold_combine(c, rec, g, nblocks, raw, st))) return rc;
         char buf[96];
         std::snprintf(buf, sizeof buf, "rs_fused_mfma_kernel<K=%d,MT=%d,NT=%d>%s%s%s", tile.K, tile.MT,
                       auto_cache_policy(tile.K, tile.MT), aligned ? "" : ",UA", inline_combine ? ",INL" : "",

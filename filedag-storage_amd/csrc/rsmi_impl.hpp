@@ -19,7 +19,8 @@
 // flag comes out of the HIP kernels (rs_kernels.hip, rs_kernels_tb.hip, rs_crc16_kernels.hip, rs_crc32_kernels.hip,
 // rs_verify_kernels.hip, rs_locate_kernels.hip, rs_heal_kernels.hip, rs_mixed_kernels.hip,
 // rs_mixed_fused_kernels.hip, rs_pair_kernels.hip, rs_heal_pair_kernels.hip, rs_scrub_kernels.hip, rs_ragged_kernels.hip).  Kernel headers: rs_gf_tile.hpp (the GF(2^8) tile pipeline), rs_verify_tile.hpp
-// (the stripe checks' tile step), rs_crc_rows.hpp (what the CRC-16 and CRC-32 rows passes share).
+// (the stripe checks' tile step), rs_crc_rows.hpp (what the CRC-16 and CRC-32 rows passes share),
+// rs_crc_fold.hpp (the CRC-16 fold on the matrix cores of the fused encode, the scrub and the mixed verify).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -556,6 +557,24 @@ int launch_encode_crc(rsmi_ctx* c, const Plan& plan, const uint8_t* in, size_t i
 int launch_plan_crc(rsmi_ctx* c, const Plan& plan, const uint8_t* in, size_t in_rs, size_t in_bs, uint8_t* out,
                     size_t out_rs, size_t out_bs, size_t S, size_t nblocks, uint32_t* raw, hipStream_t st,
                     const BlockBases* tb = nullptr, bool* armed = nullptr);
+// What the launches on the matrix-core fold (rs_crc_fold.hpp: rs_fused_mfma_kernel,
+// rs_scrub_mfma_kernel, rs_mixed_fused_kernel) and the records' combine behind them agree on, for
+// blocks of nsh rows of S bytes: chunks and tiles per row, units of 4 tiles per block, two-row
+// accumulators (a record byte per lane each), record bytes per block, and A^e, which moves a row's
+// value from the end of its last unit to the row's end.
+struct FoldGeometry {
+    uint64_t cpb, tpb, upb, nsh, nacc, rec_per_block;
+    Crc16Shift sh;
+    FoldGeometry(uint64_t S, uint64_t nsh);  // device-free (rsmi_crc.cpp)
+};
+// rs_crc16_combine_mfma_kernel over the records of nitems blocks (or list entries), g.rec_per_block
+// bytes each at rec: R(row) into out[item * g.nsh + row].  A persistent grid of up to
+// RSMI_COMBINE_WGS_PER_CU workgroups per CU, 4 waves each, over (item, 4-row group) pairs.
+#ifndef RSMI_COMBINE_WGS_PER_CU
+#define RSMI_COMBINE_WGS_PER_CU 8
+#endif
+int launch_fold_combine(rsmi_ctx* c, const uint8_t* rec, const FoldGeometry& g, uint64_t nitems, uint32_t* out,
+                        hipStream_t stream);
 int launch_encode_rows(rsmi_ctx* c, const Plan& plan, const uint8_t* in, size_t in_bs, uint8_t* out, size_t out_bs,
                        size_t S, size_t nblocks, uint32_t* d16, uint32_t* d32, hipStream_t st);
 uint8_t* coal_stage(rsmi_ctx* c, size_t need);

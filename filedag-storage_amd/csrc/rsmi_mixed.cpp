@@ -124,11 +124,11 @@ struct MixedFusedClass {
     const MixedEntry* list;
     const RsPlanDev* const* plans;
     uint8_t* base;
-    uint64_t bs, rs, S, cpb, tpb, upb;
+    uint64_t bs, rs, S;
     int K, mt;
     bool aligned;
     uint64_t entries;
-    const Crc16Shift* sh;
+    const FoldGeometry* g;  // of (S, K + mt)
     uint8_t* rec;
     uint32_t* comb;
     uint32_t* out;
@@ -141,22 +141,17 @@ int launch_mixed_fused(rsmi_ctx* c, const MixedFusedClass& a, hipStream_t stream
     uint8_t* base = a.base;
     uint8_t* rec = a.rec;
     const uint32_t* ctb = c->d_crc_tbl;
-    uint32_t nunits = uint32_t(a.entries * a.upb);
-    uint32_t S32 = uint32_t(a.S), cpb32 = uint32_t(a.cpb), tpb32 = uint32_t(a.tpb), upb32 = uint32_t(a.upb);
+    const FoldGeometry& g = *a.g;
+    uint32_t nunits = uint32_t(a.entries * g.upb);
+    uint32_t S32 = uint32_t(a.S), cpb32 = uint32_t(g.cpb), tpb32 = uint32_t(g.tpb), upb32 = uint32_t(g.upb);
     uint64_t bs64 = a.bs, rs64 = a.rs;
     void* args[] = {&dl, &dp, &base, &bs64, &rs64, &S32, &cpb32, &tpb32, &upb32, &nunits, &ctb, &rec};
     HIP_TRY(hipLaunchKernel(fn, dim3(nunits), dim3(kWG), args, 0, stream));  // a workgroup per unit
     c->split_launches.fetch_add(1, std::memory_order_relaxed);
-    // a persistent grid of up to 8 workgroups per CU over (entry, 4-slot group) items
-    uint32_t nacc32 = uint32_t((a.K + a.mt + 1) / 2), nsh32 = uint32_t(a.K + a.mt), K32 = uint32_t(a.K), n32 = a.n;
-    uint64_t ne64 = a.entries;
-    const uint8_t* crec = a.rec;
-    uint32_t* comb = a.comb;
-    Crc16Shift sh = *a.sh;
-    void* cargs[] = {&ctb, &crec, &upb32, &nacc32, &nsh32, &sh, &ne64, &comb};
-    const uint64_t items = a.entries * ((uint64_t(nsh32) + 3) / 4);
-    const uint32_t grid = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>((items + 3) / 4, uint64_t(c->num_cu) * 8)));
-    HIP_TRY(hipLaunchKernel(crc16_combine_mfma_kernel(), dim3(grid), dim3(kWG), cargs, 0, stream));
+    // the records' combine, crc16_combine_mfma_kernel() as behind the fused encode and the scrub, with
+    // the class's entries as its blocks
+    if (int rc = launch_fold_combine(c, a.rec, g, a.entries, a.comb, stream)) return rc;
+    uint32_t nsh32 = uint32_t(g.nsh), K32 = uint32_t(a.K), n32 = a.n;
     uint32_t nitems = uint32_t(a.entries * nsh32);
     const uint32_t* ccomb = a.comb;
     uint32_t* out = a.out;
@@ -215,16 +210,9 @@ int launch_mixed(rsmi_ctx* c, const MixedBatch& mb, uint8_t* base, uint64_t rs, 
     const bool any_fused = std::find(fused.begin(), fused.end(), uint8_t(1)) != fused.end();
     if (any_fused)
         if (int rc = ensure_crc_tables(c)) return rc;
-    // the fused classes' units: 4 tiles of one block each.  A^e moves a row's value from the end of
-    // its last unit to the row's end (launch_scrub's shift: S and upb alone decide it)
-    const uint64_t upb = (tpb + kFusedUnitTiles - 1) / kFusedUnitTiles;
-    Crc16Shift sh{};
-    if (any_fused) {
-        const int64_t unit_bytes = int64_t(kFusedUnitTiles) * kWave * 16;
-        const uint64_t e =
-            uint64_t(((int64_t(S) - int64_t(upb) * unit_bytes) % int64_t(kCrcOrder) + kCrcOrder) % kCrcOrder);
-        for (int b = 0; b < 16; b++) sh.col[b] = crc16_tables().shift(uint16_t(1u << b), e);
-    }
+    // the fused classes' geometry: units of 4 tiles of one block, K + mt record slots
+    std::vector<FoldGeometry> fg;
+    for (int mt = 0; any_fused && mt <= kMaxMT; mt++) fg.emplace_back(S, uint64_t(K + mt));
 
     // segments of at most 2^22 blocks whose tile counts per class stay within option launch_units_max
     const uint64_t seg =
@@ -319,7 +307,7 @@ int launch_mixed(rsmi_ctx* c, const MixedBatch& mb, uint8_t* base, uint64_t rs, 
             // records' combine with the class's entries as its blocks, and the scatter to the rows
             size_t rec_bytes = 0, comb_words = 0;
             for (int mt = 1; mt <= kMaxMT; mt++) {
-                rec_bytes += flist[mt].size() * upb * size_t((K + mt + 1) / 2) * kWave;
+                if (!flist[mt].empty()) rec_bytes += flist[mt].size() * fg[mt].rec_per_block;
                 comb_words += flist[mt].size() * size_t(K + mt);
             }
             if (rec_bytes) {
@@ -334,11 +322,10 @@ int launch_mixed(rsmi_ctx* c, const MixedBatch& mb, uint8_t* base, uint64_t rs, 
                     const uint64_t ne = flist[mt].size();
                     if (!ne) continue;
                     const MixedFusedClass fc{reinterpret_cast<const MixedEntry*>(d + flist_off[mt]), dp, sbase, bs, rs, S,
-                                             cpb, tpb, upb, K, mt, aligned, ne, &sh, rec, comb, vout, uint32_t(n)};
+                                             K, mt, aligned, ne, &fg[mt], rec, comb, vout, uint32_t(n)};
                     if ((rc = launch_mixed_fused(c, fc, stream))) return rc;
-                    const uint32_t nacc32 = uint32_t((K + mt + 1) / 2), nitems = uint32_t(ne * uint64_t(K + mt));
-                    rec += ne * upb * nacc32 * kWave;
-                    comb += nitems;
+                    rec += ne * fg[mt].rec_per_block;
+                    comb += ne * fg[mt].nsh;
                 }
             }
         }

@@ -35,21 +35,14 @@ int launch_scrub(rsmi_ctx* c, const Plan& plan, const StripeRows& rows, uint32_t
     }
     if ((rc = ensure_crc_tables(c))) return rc;
     const DevTile& tile = plan.tiles[0];
-    const uint64_t cpb = (S + 15) / 16, tpb = (cpb + kWave - 1) / kWave;
-    const uint64_t upb = (tpb + kFusedUnitTiles - 1) / kFusedUnitTiles;
-    const uint64_t nacc = (n + 1) / 2;  // two-shard accumulators: a record byte per lane each
-    const uint64_t rec_per_block = upb * nacc * kWave;
+    const FoldGeometry g(S, n);
+    const uint64_t upb = g.upb, rec_per_block = g.rec_per_block;
     // the units' records, per stream (the host pipeline runs on three)
     rsmi_ctx::VerifyScratch& sc = stream_scratch(c->scrub_scratch, stream);
     if ((rc = reserve_on(sc.p, sc.cap, nblocks * rec_per_block, stream))) return rc;
     HIP_TRY(hipMemsetAsync(bad, 0, nblocks * m * sizeof(uint32_t), stream));
-    // A^e moves a row's value from the end of its last unit to the row's end
-    const int64_t unit_bytes = int64_t(kFusedUnitTiles) * kWave * 16;
-    const uint64_t e = uint64_t(((int64_t(S) - int64_t(upb) * unit_bytes) % int64_t(kCrcOrder) + kCrcOrder) % kCrcOrder);
-    Crc16Shift sh;
-    for (int b = 0; b < 16; b++) sh.col[b] = crc16_tables().shift(uint16_t(1u << b), e);
     const RsPlanDev* pd = tile.dev;
-    uint32_t S32 = uint32_t(S), cpb32 = uint32_t(cpb), tpb32 = uint32_t(tpb), upb32 = uint32_t(upb), m32 = uint32_t(m);
+    uint32_t S32 = uint32_t(S), cpb32 = uint32_t(g.cpb), tpb32 = uint32_t(g.tpb), upb32 = uint32_t(upb), m32 = uint32_t(m);
     const uint32_t* ctb = c->d_crc_tbl;
     // launches of at most launch_units_max units (a workgroup each)
     const uint64_t max_blocks = std::max<uint64_t>(1, uint64_t(c->opt_launch_units_max) / upb);
@@ -64,15 +57,8 @@ int launch_scrub(rsmi_ctx* c, const Plan& plan, const StripeRows& rows, uint32_t
         HIP_TRY(hipLaunchKernel(fn, dim3(nunits), dim3(kWG), args, 0, stream));  // a workgroup per unit
         c->split_launches.fetch_add(1, std::memory_order_relaxed);
     }
-    // the records' combine, as behind rs_fused_mfma_kernel (launch_plan_crc): a persistent grid of
-    // up to 8 workgroups per CU, 4 waves each, over (block, 4-row group) items
-    uint32_t nacc32 = uint32_t(nacc), nsh32 = uint32_t(n);
-    uint64_t nb64 = nblocks;
-    const uint8_t* crec = sc.p;
-    void* cargs[] = {&ctb, &crec, &upb32, &nacc32, &nsh32, &sh, &nb64, &raw};
-    const uint64_t items = nblocks * ((n + 3) / 4);
-    const uint32_t grid = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>((items + 3) / 4, uint64_t(c->num_cu) * 8)));
-    HIP_TRY(hipLaunchKernel(crc16_combine_mfma_kernel(), dim3(grid), dim3(kWG), cargs, 0, stream));
+    // the records' combine, as behind rs_fused_mfma_kernel (launch_plan_crc)
+    if ((rc = launch_fold_combine(c, sc.p, g, nblocks, raw, stream))) return rc;
     return tiles_launched(c, "scrub_mfma", layout, tile);
 }
 
