@@ -11,6 +11,11 @@
  * Buffer ownership: the caller owns every buffer; the library never retains a caller
  * pointer after a call returns (cgo pointer rules).  The *_dev entry points take device
  * pointers and a hipStream_t passed as void*; they are stream-ordered and do not sync.
+ * Two exceptions: the first call of a context that needs a device table (CRC-16, CRC-32,
+ * locate) or a plan (the encode's, one per erasure pattern) allocates it and fills it with a
+ * blocking copy, which waits for work queued on the NULL stream and on every stream created without
+ * hipStreamNonBlocking (the caller's own too, if it is such a stream); and per-stream scratch
+ * that has to grow or start over waits for that stream once, as the entry points below state.
  *
  * Status codes map 1:1 onto the upstream sentinels (erasure.go:19,23 return two of them
  * directly; the rest surface through Split/Encode/Reconstruct at erasure.go:55,60,82,88).
